@@ -21,11 +21,24 @@ id % 7 == 0] select *` over 10^8 events.
 `group by k having` aggregations — over three keyed streams, K = 2^20 keys,
 2^24 events per step.
 
-Before the timed region (N=1): a parity check — a fresh runtime processes the
-first step's events and the order-sensitive digest of its device output is
-compared with oracle/cep_oracle.c's digest over the same events ("parity" in
-the JSON line) — and the CPU baseline (the same restatement sharded by key
-over the host's cores).
+Any number of steps runs in bounded memory: the input batches are generated
+a window of consecutive steps at a time (`--resident-mb`; the default 1 + 5
+steps are one window, generated before the warm-up), the clock stopped while
+the next window is generated.
+
+A plain run sets up, warms up, times the steps and prints the line.  With
+`--full`, before the timed region (N=1): a parity check — a fresh runtime
+processes the first step's events and the order-sensitive digest of its device
+output is compared with oracle/cep_oracle.c's digest over the same events
+("parity" in the JSON line) — and the CPU baseline (the same restatement
+sharded by key over the host's cores); `--no-parity` / `--no-cpu` drop either.
+
+`--dump-outputs DIR` (N=1) writes the output rows of the last timed step, read
+from the engine between that step's send and its flush (the clock is stopped
+meanwhile), as DIR/<output>.npy: float64 [rows, 1 + columns] = event ts, then
+the select columns, rows sorted by every column (the device's emission order
+between keys is not fixed), a seeded sample of them if the output is large;
+DIR/row_counts.npy holds each output's full row count.
 
 Prints ONE JSON line (rank 0).
 """
@@ -71,8 +84,17 @@ def parse():
     ap.add_argument("--chunk", type=int, default=1 << 25)
     ap.add_argument("--buckets-log2", type=int, default=0,
                     help="key buckets = 2^n (0: engine default, <= 512 keys per bucket)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle parity check")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the oracle parity check and the CPU baseline before the timed region "
+                         "(1 GPU; off by default: a plain run only sets up, warms up and times its steps)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the oracle parity check")
+    ap.add_argument("--resident-mb", type=int, default=0,
+                    help="input batches kept resident at a time, in MiB per GPU (0: a quarter of the device's "
+                         "memory); more steps than that are generated window by window, off the clock")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="1 GPU: write the last timed step's output rows as DIR/<output>.npy (float64, sorted, "
+                         "a seeded sample of a large output) and DIR/row_counts.npy")
     ap.add_argument("--exchange", choices=["padded", "twophase"], default="padded",
                     help="key shuffle (pattern records / config-5 rows): fixed owner segments with in-band "
                          "counts (no host round trip per step) or counts first, then an exact alltoallv")
@@ -96,7 +118,12 @@ def parse():
                          "default)")
     ap.add_argument("--parity-steps", type=int, default=4,
                     help="config 5: steps of the stream the parity check covers (fresh state)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    return args
 
 
 def _free_port():
@@ -452,6 +479,40 @@ def config5_parity(args, opts, n, steps):
     return res, cpu, sel
 
 
+# ----------------------------------------------------------- --dump-outputs --
+DUMP_BUDGET_BYTES = 48 << 20    # all files of one dump together (< 64 MB)
+DUMP_SEED = 20240607
+
+
+def dump_sample(ts, cols, budget):
+    """The rows (event ts, select columns) of one output as a float64 host
+    array [rows, 1 + columns] in a run-independent order (sorted by every
+    column, first column most significant); more than `budget` bytes of them:
+    the rows at seeded positions of that order.  int32 columns and the
+    millisecond timestamps are exact in float64.  Returns (array, row count)."""
+    import numpy as np
+    import torch
+    m = int(ts.shape[0])
+    rows = torch.stack([ts.double()] + [c.double() for c in cols], dim=1)
+    idx = torch.arange(m, device=rows.device)
+    for c in reversed(range(rows.shape[1])):
+        idx = idx[torch.argsort(rows[idx, c], stable=True)]
+    cap = max(1, budget // (8 * rows.shape[1]))
+    if m > cap:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(m, size=cap, replace=False))
+        idx = idx[torch.from_numpy(pick).to(idx.device)]
+    return rows[idx].cpu().numpy(), m
+
+
+def write_dump(path, dumped):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for o, (rows, _) in dumped.items():
+        np.save(os.path.join(path, o + ".npy"), rows)
+    # full row count of every output, in the order of the app's outputs
+    np.save(os.path.join(path, "row_counts.npy"), np.array([m for _, m in dumped.values()], dtype=np.float64))
+
+
 # ------------------------------------------------------------------- main --
 def main():
     args = parse()
@@ -485,17 +546,18 @@ def main():
         plan = workload.FILTER_PLAN
         opts = dict(device=local, profile=PROFILE_EVERY, ordered_output=0)
 
-    # parity + CPU baseline first (N=1): the host leg needs the same events
+    # --full: parity + CPU baseline first (N=1): the host leg needs the same events
     parity, cpu, kept = None, None, None
     c5_sel = C5_AGG_SEL_BYTES
+    checks = args.full and world == 1 and not (args.no_parity and args.no_cpu)
     if config5:
-        if world == 1 and not (args.no_parity and args.no_cpu):
+        if checks:
             parity, cpu, c5_sel = config5_parity(args, opts, n, args.parity_steps)
             if args.no_parity:
                 parity = None
             if args.no_cpu:
                 cpu = None
-    elif world == 1 and not (args.no_parity and args.no_cpu):
+    elif checks:
         if pattern:
             parity, w, kept = pattern_parity(args, n, opts)
             if not args.no_cpu:
@@ -517,16 +579,17 @@ def main():
         opts["omit_seq"] = 1
     rt = fs.SiddhiAppRuntime(plan, **opts)
 
-    # Inputs for every step, generated on the device before the timed region.
-    # Multi-GPU ingest: "shuffle" (default) — rank r holds global index range
+    # Inputs for every step, generated on the device before the timed region
+    # (more steps than fit the resident-input budget: window by window, the
+    # clock stopped between windows, see below).  Multi-GPU ingest: "shuffle" (default) — rank r holds global index range
     # r of each step and the engine routes it (push-down + owner = k % world),
     # RCCL all-to-all moves the records, each owner walks what it received;
     # "prepartitioned" — the input is already keyed upstream (Flink keyBy):
     # rank r draws only keys it owns, no exchange.
     shuffle_mode = (pattern or config5) and world > 1 and args.ingest == "shuffle"
     host_ingest = args.ingest in ("host", "host-pageable") and world == 1
-    batches = []
-    for s in range(warm + steps):
+
+    def make_batch(s):
         first = (s * world + rank) * n
         d = workload.generate_device(first, n, args.keys, rate=args.rate,
                                      single_stream=not pattern, device="cuda")
@@ -542,8 +605,18 @@ def main():
         if host_ingest:   # the batch lives in host memory; the engine stages it over PCIe
             d = {c: (v.cpu().pin_memory() if args.ingest == "host" else v.cpu()).numpy()
                  if hasattr(v, "cpu") else v for c, v in d.items()}
-        batches.append(d)
-    torch.cuda.synchronize()
+        return d
+
+    # A batch of config 3 is 6.7 GB, so only a window of consecutive steps is
+    # kept resident: at most --resident-mb of inputs (default: a quarter of
+    # the device's memory, the same on every rank).  A run whose steps all
+    # fit (the default 1 + 5 do) has one window, generated before the warm-up.
+    total = warm + steps
+    batch0 = make_batch(0)
+    batch_bytes = sum(int(v.nbytes) if hasattr(v, "nbytes") else v.numel() * v.element_size()
+                      for v in batch0.values() if hasattr(v, "shape"))
+    resident = (args.resident_mb << 20) or torch.cuda.get_device_properties(local).total_memory // 4
+    window = max(1, resident // max(1, batch_bytes))
 
     bufs = {}
     delivered = [0]
@@ -629,31 +702,70 @@ def main():
                 cur = route(blist[i + 1], 1 - j)
         rt.flush()
 
-    def step(d):
+    dumped = {}
+    paused = [0.0]
+
+    dump_outs = workload.CONFIG5_OUTPUTS if config5 else ["O"]
+
+    def grab():
+        # --dump-outputs: the last timed step's rows are read while the engine
+        # still holds them (flush consumes them); the step's kernels are waited
+        # for on the clock, the reading itself is taken off it
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for o in dump_outs:
+            ts, _, cols = rt.output_tensors(o, copy=False)
+            dumped[o] = dump_sample(ts, cols, DUMP_BUDGET_BYTES // len(dump_outs))
+        torch.cuda.synchronize()
+        paused[0] += time.perf_counter() - t
+
+    def step(d, before_flush=None):
         if pattern or config5:
             rt.send("A", d["ts"], [d["k"], d["ts"], d["id"], d["price"]], streams=d["stream"])
         else:
             rt.send("inputStream", d["ts"], [d["id"], d["name"], d["price"], d["ts"]])
+        if before_flush is not None:
+            before_flush()
         rt.flush()
 
-    if shuffle_mode:
-        run_shuffle(batches[:warm])
-    else:
-        for s in range(warm):
-            step(batches[s])
-    st0 = rt.stats()
-    d0 = delivered[0]
-    barrier(world)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    if shuffle_mode:
-        run_shuffle(batches[warm:])
-    else:
-        for s in range(steps):
-            step(batches[warm + s])
-    torch.cuda.synchronize()
-    barrier(world)
-    dt = time.perf_counter() - t0
+    # Window by window: generate its batches (off the clock), run its warm-up
+    # steps, then time its timed steps as one region.  Every step already ends
+    # in a flush that waits for the device, so a region split between two
+    # windows times the same work as an unsplit one.
+    st0, d0, dt = None, 0, 0.0
+    batches = None
+    for w0 in range(0, total, window):
+        w1 = min(w0 + window, total)
+        batches = None      # the previous window's inputs go before the next are made
+        batches = [batch0 if s == 0 else make_batch(s) for s in range(w0, w1)]
+        batch0 = None
+        torch.cuda.synchronize()
+        nwarm = max(0, min(warm, w1) - w0)
+        if shuffle_mode:
+            run_shuffle(batches[:nwarm])
+        else:
+            for d in batches[:nwarm]:
+                step(d)
+        if w1 <= warm:
+            continue
+        if st0 is None:
+            st0 = rt.stats()
+            d0 = delivered[0]
+        barrier(world)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if shuffle_mode:
+            run_shuffle(batches[nwarm:])
+        else:
+            for s in range(w0 + nwarm, w1):
+                step(batches[s - w0], grab if args.dump_outputs and s == total - 1 else None)
+        torch.cuda.synchronize()
+        barrier(world)
+        dt += time.perf_counter() - t0
+    del batches
+    dt -= paused[0]
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, dumped)
     st1 = rt.stats()
     dt_max = reduce_over_ranks(world, dt, "max")
     events_total = reduce_over_ranks(world, float(n * steps), "sum")

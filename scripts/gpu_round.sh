@@ -12,15 +12,15 @@ if [ "$PART" = 1 ]; then
 scripts/gpu_steps.sh \
   "450 gputest python -u -m pytest tests -m gpu -v --timeout 150 --timeout-method thread" \
   "120 smoke python -c 'import __graft_entry__ as g; g.smoke()'" \
-  "300 b3 python -u bench.py" \
+  "300 b3 python -u bench.py --full" \
   "300 s3 cd /tmp && $P $R/gpurun_out/s3 -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu --no-parity" \
-  "300 b5 python -u bench.py --workload config5" \
+  "300 b5 python -u bench.py --full --workload config5" \
   "200 s5 cd /tmp && $P $R/gpurun_out/s5 -- python3 $R/bench.py --workload config5 --steps 3 --warmup 1 --no-cpu --no-parity"
 elif [ "$PART" = 2 ]; then
 scripts/gpu_steps.sh \
-  "200 b2 python -u bench.py --workload filter" \
+  "200 b2 python -u bench.py --full --workload filter" \
   "200 s2 cd /tmp && $P $R/gpurun_out/s2 -- python3 $R/bench.py --workload filter --steps 3 --warmup 1 --no-cpu --no-parity" \
-  "300 bz python -u bench.py --keys-dist zipf" \
+  "300 bz python -u bench.py --full --keys-dist zipf" \
   "200 bdo python -u bench.py --deliver --ordered --no-cpu --no-parity" \
   "200 bd python -u bench.py --deliver --no-cpu --no-parity" \
   "200 bdseq python -u bench.py --deliver --ordered --with-seq --no-cpu --no-parity" \

@@ -9,18 +9,18 @@ case "$1" in
 1) scripts/gpu_steps.sh \
   "500 gputest python -u -m pytest tests -m gpu -v --timeout 150 --timeout-method thread" \
   "150 smoke python -c 'import __graft_entry__ as g; g.smoke()'" \
-  "300 b3 python -u bench.py" \
-  "300 b3t0 python -u bench.py --ts-order 0 --no-cpu" \
+  "300 b3 python -u bench.py --full" \
+  "300 b3t0 python -u bench.py --full --ts-order 0 --no-cpu" \
   "300 s3 cd /tmp && $P $R/gpurun_out/s3 -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu --no-parity" \
   "300 s3t0 cd /tmp && $P $R/gpurun_out/s3t0 -- python3 $R/bench.py --ts-order 0 --steps 3 --warmup 1 --no-cpu --no-parity" ;;
 2) scripts/gpu_steps.sh \
   "400 pmc3 bash scripts/gpu_pmc.sh r06_pmc_config3.json" \
   "400 pmc3t0 env BENCH_ARGS='--ts-order 0' bash scripts/gpu_pmc.sh r06_pmc_config3_ts_order0.json" ;;
 3) scripts/gpu_steps.sh \
-  "300 b2 python -u bench.py --workload filter" \
-  "300 bz python -u bench.py --keys-dist zipf --no-cpu" \
-  "300 bzt0 python -u bench.py --keys-dist zipf --ts-order 0 --no-cpu" \
-  "300 b5 python -u bench.py --workload config5" \
+  "300 b2 python -u bench.py --full --workload filter" \
+  "300 bz python -u bench.py --full --keys-dist zipf --no-cpu" \
+  "300 bzt0 python -u bench.py --full --keys-dist zipf --ts-order 0 --no-cpu" \
+  "300 b5 python -u bench.py --full --workload config5" \
   "200 bdo python -u bench.py --deliver --ordered --no-cpu --no-parity" \
   "200 bh python -u bench.py --ingest host --no-cpu --no-parity" \
   "200 s5 cd /tmp && $P $R/gpurun_out/s5 -- python3 $R/bench.py --workload config5 --steps 3 --warmup 1 --no-cpu --no-parity" \

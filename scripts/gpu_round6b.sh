@@ -13,15 +13,15 @@ a) scripts/gpu_steps.sh \
 b) scripts/gpu_steps.sh \
   "500 gputest python -u -m pytest tests -m gpu -v --timeout 150 --timeout-method thread" \
   "150 smoke python -c 'import __graft_entry__ as g; g.smoke()'" \
-  "300 b3 python -u bench.py" \
-  "300 b3t0 python -u bench.py --ts-order 0 --no-cpu" \
-  "300 b2 python -u bench.py --workload filter" \
+  "300 b3 python -u bench.py --full" \
+  "300 b3t0 python -u bench.py --full --ts-order 0 --no-cpu" \
+  "300 b2 python -u bench.py --full --workload filter" \
   "300 s3 cd /tmp && $P $R/gpurun_out/s3 -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu --no-parity" \
   "300 s3t0 cd /tmp && $P $R/gpurun_out/s3t0 -- python3 $R/bench.py --ts-order 0 --steps 3 --warmup 1 --no-cpu --no-parity" \
   "200 s2 cd /tmp && $P $R/gpurun_out/s2 -- python3 $R/bench.py --workload filter --steps 3 --warmup 1 --no-cpu --no-parity" ;;
 c) scripts/gpu_steps.sh \
-  "300 bz python -u bench.py --keys-dist zipf --no-cpu" \
-  "300 bzt0 python -u bench.py --keys-dist zipf --ts-order 0 --no-cpu" \
-  "300 b5 python -u bench.py --workload config5" \
+  "300 bz python -u bench.py --full --keys-dist zipf --no-cpu" \
+  "300 bzt0 python -u bench.py --full --keys-dist zipf --ts-order 0 --no-cpu" \
+  "300 b5 python -u bench.py --full --workload config5" \
   "200 own python -u scripts/owner_bench.py" ;;
 esac
