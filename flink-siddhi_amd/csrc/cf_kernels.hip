@@ -132,6 +132,18 @@ __global__ __launch_bounds__(kCfPartThreads, CF_PART_MINW) void k_cfpart(CfPartA
   // the order-tolerant fallback of an adaptive chunk runs only when that
   // chunk turned out not to be in order (uniform: one word)
   if (TOL && a.gate && *(volatile const uint32_t*)a.gate != a.gate_seq) return;
+  // A CU runs its tiles one after another and each tile is a load phase
+  // (HBM) followed by LDS phases (no HBM reads).  Workgroups that start
+  // together share HBM fairly, so they finish their loads together and stay
+  // in step for the whole launch: every CU loads while HBM is saturated, then
+  // every CU works in LDS while HBM idles.  The first round of workgroups
+  // (one per CU) therefore starts spread over about one tile's duration, 32
+  // steps per XCD; later workgroups inherit the offset of the one they follow.
+  if (a.stagger > 0 && blockIdx.x < kCfStaggerBlocks) {
+    const uint64_t t0 = __builtin_amdgcn_s_memtime();
+    const uint64_t d = (uint64_t)((blockIdx.x >> 3) & 31u) * (uint64_t)a.stagger;
+    while (__builtin_amdgcn_s_memtime() - t0 < d) __builtin_amdgcn_s_sleep(8);
+  }
   const PatternArgs& p = a.pat;
   // high-water mark of every row consumed before this chunk (max of the 64
   // shards): ATL tiles 0 / last compare and carry it, TOL tiles carry it
@@ -214,9 +226,14 @@ __global__ __launch_bounds__(kCfPartThreads, CF_PART_MINW) void k_cfpart(CfPartA
       if (bad) report_descent(a.rows, a.err);
     }
   }
+  // a full tile (uniform; every tile of a chunk but a ragged last one) issues
+  // all of its loads, the previous row's ts included, before it waits once
+  const bool full = !FR && (tile + 1) * (int64_t)kCfTile <= a.rows.n;
   if (!FR && valid) {
     uint32_t sb[E];
-    cf_load_cols<E, NP>(a.rows, a.pref, a.ts_slot, row0, valid, tsv, sb, pv);
+    int64_t before_full = 0;
+    if (full) cf_load_cols_full<E, NP>(a.rows, a.pref, a.ts_slot, row0, tsv, sb, pv, &before_full);
+    else cf_load_cols<E, NP>(a.rows, a.pref, a.ts_slot, row0, valid, tsv, sb, pv);
     uint32_t is_a = 0, is_b = 0;
 #pragma unroll
     for (int e = 0; e < E; ++e) {
@@ -233,6 +250,8 @@ __global__ __launch_bounds__(kCfPartThreads, CF_PART_MINW) void k_cfpart(CfPartA
       int64_t before;
       if (ATL && r0 == 0) {
         before = (int64_t)(s_hwm ^ kHwmBias);
+      } else if (full) {
+        before = row0 > 0 ? before_full : batch_prev_ts(a.rows);
       } else {
         before = row0 > 0 ? a.rows.ts[row0 - 1] : batch_prev_ts(a.rows);
       }
@@ -291,6 +310,20 @@ __global__ __launch_bounds__(kCfPartThreads, CF_PART_MINW) void k_cfpart(CfPartA
   // bits 0-12 rank in tile, 13-24 bucket, 25-27 role (never all ones)
   uint32_t packed[E];
   uint32_t lkey[E];
+  // hot-key diversion: the hot slots of a lane's rows, looked up as one group
+  // of loads (a row with no role or a key out of range reads entry 0 and
+  // ignores it), not one waited load per row inside the histogram loop
+  uint32_t hsv[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) hsv[e] = kNotHot;
+  if (!ATL && a.nhot) {   // uniform
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const bool role = (((role_a | role_b | (TOL ? role_pb : 0u)) >> e) & 1u) != 0;
+      const int64_t kfield = shard_key((int64_t)fkey[e], p.key_stride, p.key_offset);
+      hsv[e] = a.hot_id[(role && kfield >= 0 && kfield < p.key_capacity) ? kfield : 0];
+    }
+  }
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     packed[e] = 0xffffffffu;
@@ -312,7 +345,7 @@ __global__ __launch_bounds__(kCfPartThreads, CF_PART_MINW) void k_cfpart(CfPartA
       // P + bucket (the walk takes the key's latest ts from them)
       if (role == kRolePB) bucket += (uint32_t)P;
     } else if (a.nhot) {
-      const uint32_t hs = a.hot_id[kfield];
+      const uint32_t hs = hsv[e];
       if (hs != kNotHot) {   // hot key: its own bucket; the key field holds the slot
         bucket = (uint32_t)P + hs;
         lkey[e] = hs;

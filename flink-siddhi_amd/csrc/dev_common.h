@@ -277,6 +277,86 @@ __device__ __forceinline__ void cf_load_cols(const RowsArgs& rows, const PrefPla
     }
 }
 
+// cf_load_cols for a full tile (every row of every lane lies in the slice:
+// uniform per workgroup), plus the ts of the row before the lane's first
+// (`before`; rows.ts[0] again for batch row 0, which the caller replaces).
+// Same load instructions as above — one base per column, rows at immediate
+// offsets 64 e — but nothing between them: no per-lane condition, no
+// conversion, no select.  The uniform type branch holds raw loads only (a
+// 32-bit or 1-byte column: one register per row), so its join merges
+// registers still in flight and does not wait; sign extension, bool -> 0 / 1
+// and the widening to VM words come after the last load is issued, as
+// selects on the (uniform) type.  Above, each `valid ? load : 0` and each
+// conversion inside a type arm ends in s_waitcnt vmcnt(0): about 12
+// dependent HBM round trips per tile instead of one.
+template <int E, int Q = kPref>
+__device__ __forceinline__ void cf_load_cols_full(const RowsArgs& rows, const PrefPlan& pref, int ts_slot,
+                                                  int64_t row0, uint64_t (&tsv)[E], uint32_t (&sb)[E],
+                                                  uint64_t (&pv)[Q][E], int64_t* before) {
+  const int64_t* tp = rows.ts + row0;
+  // (first, in the block of the ts loads: after the last type branch the
+  // scheduler would place it behind the first waits of the decode)
+  *before = rows.ts[row0 > 0 ? row0 - 1 : 0];
+#pragma unroll
+  for (int e = 0; e < E; ++e) tsv[e] = (uint64_t)tp[64 * e];
+  // (no stream column: the same byte loads from the lane's ts rows, which are
+  // in bounds, and the handle selected afterwards: no arm that overwrites
+  // registers of loads in flight)
+  const uint8_t* sp = rows.stream ? rows.stream + row0 : (const uint8_t*)tp;
+  uint32_t sraw[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) sraw[e] = (uint32_t)sp[64 * e];
+  uint32_t lo[Q][E], hi[Q][E];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int c = pref.col[q];
+    const int ty = rows.cols.t[c];
+    const void* base = rows.cols.p[c];
+    if (q < pref.n && q != ts_slot && (ty == T_LONG || ty == T_DOUBLE)) {
+      const uint64_t* b = (const uint64_t*)base + row0;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const uint64_t x = b[64 * e];
+        lo[q][e] = (uint32_t)x;
+        hi[q][e] = (uint32_t)(x >> 32);
+      }
+    } else if (q < pref.n && q != ts_slot && ty == T_BOOL) {
+      const uint8_t* b = (const uint8_t*)base + row0;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        lo[q][e] = (uint32_t)b[64 * e];
+        hi[q][e] = 0;
+      }
+    } else if (q < pref.n && q != ts_slot) {
+      const uint32_t* b = (const uint32_t*)base + row0;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        lo[q][e] = b[64 * e];
+        hi[q][e] = 0;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < E; ++e) lo[q][e] = hi[q][e] = 0;
+    }
+  }
+  // every load is in flight: decode
+#pragma unroll
+  for (int e = 0; e < E; ++e) sb[e] = rows.stream ? sraw[e] : (uint32_t)rows.input;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int ty = rows.cols.t[pref.col[q]];
+    const bool wide = ty == T_LONG || ty == T_DOUBLE;
+    const bool sext = !wide && ty != T_BOOL && ty != T_FLOAT;   // from_i32
+    const bool isb = ty == T_BOOL;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const uint32_t l = isb ? (lo[q][e] ? 1u : 0u) : lo[q][e];
+      const uint32_t h = sext ? (uint32_t)((int32_t)lo[q][e] >> 31) : hi[q][e];
+      pv[q][e] = q == ts_slot ? tsv[e] : (((uint64_t)h << 32) | l);
+    }
+  }
+}
+
 // Inclusive scan over the 64 lanes with DPP row shifts and row broadcasts
 // (VALU-only: no LDS round trip per step, unlike __shfl_up).
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {

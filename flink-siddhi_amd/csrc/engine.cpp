@@ -1397,6 +1397,42 @@ bool cf_plan(const PatternRT& rt, const RowsArgs& rows, CfPlan* cf, bool from_re
   return true;
 }
 
+// A prefetch slot whose column IS the batch's event-ts buffer holds a copy of
+// the ts registers (E x 2 VGPRs).  When the column is only carried (rebuilt
+// from the record ts: cap_phys / bcol_phys = -1) and is neither the key nor a
+// term's column, nothing reads that copy: the partition is launched without
+// the slot, with the later slots moved down by one (config 3: the NP = 3
+// instance, which does not spill, instead of NP = 4).
+void cf_drop_ts_slot(CfPartArgs* pa) {
+  const int ts = pa->ts_slot;
+  PrefPlan& pf = pa->pref;
+  if (ts < 0 || pa->in_recs || pf.n < 2 || pf.key_slot == ts) return;
+  const PatternArgs& p = pa->pat;
+  const int nf = p.f_prog >= 0 ? p.f_terms.n : 0, ng = p.g_raw_prog >= 0 ? p.g_terms.n : 0;
+  for (int i = 0; i < nf; ++i)
+    if (pf.f_slot[i] == ts) return;
+  for (int i = 0; i < ng; ++i)
+    if (pf.g_slot[i] == ts) return;
+  // (cf_plan lists only the physical carried words: a ts alias is not among
+  // them; words past the stream's own count are padding nobody reads)
+  for (int w = 0; w < pa->cf.nw; ++w)
+    if (pa->cf.a_slot[w] == ts || pa->cf.b_slot[w] == ts) return;
+  auto down = [&](int32_t& s) {
+    if (s > ts) --s;
+  };
+  for (int i = ts; i + 1 < pf.n; ++i) pf.col[i] = pf.col[i + 1];
+  --pf.n;
+  for (int i = pf.n; i < kPref; ++i) pf.col[i] = pf.col[0];
+  for (int i = 0; i < nf; ++i) down(pf.f_slot[i]);
+  for (int i = 0; i < ng; ++i) down(pf.g_slot[i]);
+  for (int w = 0; w < 2; ++w) {
+    down(pa->cf.a_slot[w]);
+    down(pa->cf.b_slot[w]);
+  }
+  down(pf.key_slot);
+  pa->ts_slot = -1;
+}
+
 // Closed-form fast path: k_cfpart(c) then k_cfwalk(c) per chunk (double-
 // buffered arenas; CEP_OVERLAP=1 runs the partitions on the side stream).
 // tol: the order-tolerant closed form (ts in any order: g-failing B rows kept
@@ -1448,11 +1484,19 @@ int run_pattern_cf(cep_app* a, PatternRT& rt, const Query& q, OutStream& o,
     pa.pat = rt.pa;
     pa.pat.tolerant = tol ? 1 : 0;
     pa.cf = cf;
+    cf_drop_ts_slot(&pa);
     pa.chunk_base = (int64_t*)rt.chunk_base[b].p;
     pa.recs = (uint64_t*)rt.cf_recs[b].p;
     pa.tile_off = (uint16_t*)rt.cf_toff[b].p;
     pa.ntiles = (int32_t)ntiles;
     pa.err = (unsigned int*)a->err.p;
+    // staggered first round (k_cfpart): 32 steps over about one tile's
+    // duration (~40 k ticks at config 3; measured 320 / 640 / 1280 / 2000
+    // ticks per step: 293 / 285 / 281 / 286 us), and only when
+    // every CU runs several tiles, so a short chunk does not pay the delay
+    // (CEP_CF_STAGGER: ticks per step, 0 = off)
+    static const int stagger = std::getenv("CEP_CF_STAGGER") ? std::atoi(std::getenv("CEP_CF_STAGGER")) : 1280;
+    pa.stagger = ntiles >= 4 * kCfStaggerBlocks ? stagger : 0;
     // the pool cursor of this chunk's walk: zeroed by the partition (serial
     // mode), or by a fill on the walk's stream when the partition may run
     // beside the previous walk (CEP_OVERLAP)

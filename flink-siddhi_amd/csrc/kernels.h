@@ -341,7 +341,11 @@ struct CfPartArgs {
   // the walk's pending-pool cursor, zeroed by tile 0 (the walk of this chunk
   // runs after this kernel; no separate fill launch between them)
   unsigned long long* pool_cursor;
+  // ticks between the starts of the first kCfStaggerBlocks workgroups' phases
+  // (0: all start together), see k_cfpart
+  int32_t stagger;
 };
+constexpr int kCfStaggerBlocks = 256;   // one workgroup per CU in the first round (MI355X: 256 CUs)
 
 struct CfWalkArgs {
   PatternArgs pat;
