@@ -165,6 +165,10 @@ struct PatternRT {
   // a pattern whose result depends on event-time order (`within`, not a
   // sequence): with cep_options.ts_order = 0 it runs the order-tolerant path
   bool order_sensitive = false;
+  // sliding-window aggregate (win_kernels.hip): the window fields of WinArgs
+  // (kind, param, ring, entry layout); win.kind = WIN_NONE: not a window query
+  WinArgs win{};
+  bool win_vm = false;         // k_winwalk needs the interpreter (having, computed select items)
 };
 
 // Multi-query group (mq_kernels.hip): keyed queries of one app sharing a
@@ -420,6 +424,8 @@ bool mq_candidate(const cep_app* a, const Query& q, MqNeeds* nd) {
     if (std::find(nd->carry.begin(), nd->carry.end(), col) == nd->carry.end()) nd->carry.push_back(col);
   };
   if (q.kind == Q_AGG) {
+    // a windowed aggregate keeps a ring per key: its own pipeline (k_winwalk)
+    if (q.win_kind != WIN_NONE) return false;
     if (q.in_stream < 0 || !key_ok(q.in_stream, q.key_col)) return false;
     if ((int)q.aggs.size() > kMqMaxAggs || !q.having_simple || (int)q.select.size() > kMqMaxSel) return false;
     if (q.f.valid() && q.f_terms.n < 0) return false;
@@ -974,11 +980,53 @@ int create_runtime(cep_app* a) {
     if (q.kind != Q_PATTERN && q.kind != Q_AGG) continue;
     if (a->in_mq[qi]) continue;   // served by a multi-query group
     const bool agg = q.kind == Q_AGG;
-    // group-by state: one slot of (accumulator, count) pairs per group
+    const bool win = agg && q.win_kind != WIN_NONE;
+    // group-by state: one slot of (accumulator, count) pairs per group (a
+    // window query: one slot of accumulators + the ring, kernels.h WinArgs)
     const int S = agg ? 1 : a->opt.pending_slots;
     PatternRT rt;
     rt.q = (int)qi;
     PatternArgs& p = rt.pa;
+    if (win) {
+      // Case (c), `group by k` + #window.time outside a partition: Siddhi's
+      // window spans every group, the engine keeps one per key.  With
+      // non-decreasing ts the global window's front pops are monotone in ts:
+      // when row e arrives, the rows popped so far are exactly those with
+      // ts + T <= e.ts (every row before a blocked front has a ts >= the
+      // front's, so none of them is due either).  A group's accumulator may
+      // take its removes lazily, at the group's next own row e: nothing reads
+      // it in between, and the rows of the group removed before add(e) are
+      // then exactly the group's rows with ts + T <= e.ts, oldest first — what
+      // the per-key window pops at e.  With ts in any order a front row of
+      // another group can block (or release) this group's rows, so the two
+      // differ.
+      if (q.win_global && a->opt.ts_order != 1)
+        return fail(a, CEP_E_UNSUPPORTED,
+                    "group by with #window.time outside a partition is not supported with ts_order = 0: Siddhi's "
+                    "window spans every group, and one window per group equals it only for non-decreasing "
+                    "timestamps (set ts_order = 1, or partition the query)");
+      if (q.win_kind == WIN_LENGTH && q.win_param > kWinMaxRing)
+        return fail(a, CEP_E_CAPACITY, "#window.length(" + std::to_string(q.win_param) + ") exceeds the capacity of " +
+                                           std::to_string(kWinMaxRing) + " window rows per key");
+      WinArgs& w = rt.win;
+      w.kind = q.win_kind;
+      w.param = q.win_param;
+      w.ring = q.win_kind == WIN_LENGTH ? (int)q.win_param : a->opt.pending_slots;
+      w.nval = 0;
+      for (size_t i = 0; i < q.aggs.size(); ++i) {
+        w.agg_val[i] = -1;
+        if (q.aggs[i].word < 0) continue;
+        for (int v = 0; v < w.nval; ++v)
+          if (w.val_word[v] == q.aggs[i].word) w.agg_val[i] = v;
+        if (w.agg_val[i] < 0) {
+          w.val_word[w.nval] = q.aggs[i].word;
+          w.agg_val[i] = w.nval++;
+        }
+      }
+      w.entry_words = w.nval + (q.win_kind == WIN_TIME ? 1 : 0);
+      rt.win_vm = q.having.valid();
+      for (auto& it : q.select) rt.win_vm |= it.src == SRC_VM;
+    }
     p.a_stream = q.a_stream;
     p.b_stream = q.b_stream;
     p.f_prog = q.f.off;
@@ -998,8 +1046,11 @@ int create_runtime(cep_app* a) {
     for (int i = 0; i < p.ncap; ++i) p.cap_from_rec[i] = q.cap_from_rec[i];
     p.rec_words = 2 + std::max(p.nrec_a, p.nrec_b);
     p.slot_words = agg ? 2 * (int)q.aggs.size() : 2 + p.ncap;
+    if (win) p.slot_words = (int)q.aggs.size() + rt.win.ring * rt.win.entry_words;
     p.key_words = 1 + S * p.slot_words;
     p.pending_slots = S;
+    // case (c) relies on event-time order: the partition pass checks it
+    if (win && q.win_global) p.within = q.win_param;
     // closed form keeps each record's carried words in LDS (kWalkCapLds)
     p.closed_form = (!agg && q.every && !q.g_in_walk && p.rec_words <= 2 + kWalkCapLds) ? 1 : 0;
     p.agg_mode = agg ? 1 : 0;
@@ -1069,12 +1120,24 @@ int create_runtime(cep_app* a) {
     const int64_t kc = kcap;
     const int64_t kpb = (kc + (1 << lg) - 1) >> lg;
     rt.kstride = kpb << lg;
+    if (win) {
+      // the rings are the one state here that grows with a plan constant
+      const double bytes = (double)rt.kstride * p.slot_words * 8;
+      size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > (double)free_b)
+        return fail(a, CEP_E_CAPACITY, "window state of " + std::to_string((unsigned long long)bytes) + " bytes (" +
+                                           std::to_string(rt.kstride) + " keys x " + std::to_string(p.slot_words) +
+                                           " words) exceeds the GPU's memory capacity: lower key_capacity" +
+                                           (q.win_kind == WIN_TIME ? " or pending_slots" : ""));
+    }
     if (!dev_ensure(&rt.khdr, (size_t)rt.kstride * 4, a->stream, false) ||
         !dev_ensure(&rt.kslot, (size_t)rt.kstride * bank * S * p.slot_words * 8, a->stream, false) ||
         !dev_ensure(&rt.chunk_base[0], 64, a->stream, false) ||
         !dev_ensure(&rt.chunk_base[1], 64, a->stream, false))
       return fail(a, CEP_E_DEVICE, "out of device memory (pattern state)");
     hipMemset(rt.khdr.p, 0, (size_t)rt.kstride * 4);
+    // (snapshots store a live key's whole slot: free ring entries read as zero)
+    if (win) hipMemset(rt.kslot.p, 0, (size_t)rt.kstride * bank * S * p.slot_words * 8);
     // the walk build decides the chunk cap (its LDS segment tables)
     bool walk_vm = q.g_in_walk || agg || q.nfa;
     for (auto& it : q.select) walk_vm |= it.src == SRC_VM;
@@ -1768,6 +1831,12 @@ int run_pattern(cep_app* a, PatternRT& rt, const RowsArgs& rows_in,
       !rows_in.seq)
     tolerant = true;
   const RowsArgs& rows_all = rows_in;
+  // case (c) of the window queries (one window per group standing in for
+  // Siddhi's global one) holds for non-decreasing ts only: released late rows
+  // are not
+  if (tolerant && rt.win.kind != WIN_NONE && q.win_global)
+    return fail(a, CEP_E_UNSUPPORTED, "group by with #window.time outside a partition is not supported for late rows "
+                                      "(late_policy 2): partition the query");
   // ts in any order on the closed form (k_cfpart / k_cfwalk TOL builds);
   // CEP_TOL_GENERAL=1 keeps the N-state walk (nfa_pair) for these runs
   static const bool tol_general = std::getenv("CEP_TOL_GENERAL") != nullptr;
@@ -1883,6 +1952,28 @@ int run_pattern(cep_app* a, PatternRT& rt, const RowsArgs& rows_in,
     wa.kstride = rt.kstride;
     wa.out = out_args(o, q);
     wa.err = pa.err;
+    if (rt.win.kind != WIN_NONE) {
+      WinArgs ww = rt.win;
+      ww.vm = pa.vm;
+      ww.pat = pa.pat;
+      ww.recs = pa.recs;
+      ww.tile_off = pa.tile_off;
+      ww.ntiles = (int)ntiles;
+      ww.tile_rows = pa.tile_rows;
+      ww.chunk_base = wa.chunk_base;
+      ww.khdr = wa.khdr;
+      ww.kslot = wa.kslot;
+      ww.kstride = wa.kstride;
+      ww.out = wa.out;
+      ww.err = wa.err;
+      {
+        LaunchTimer t(a, CEP_K_AGG);
+        launch_winwalk(ww, P, rt.win_vm, a->stream);
+      }
+      hipEventRecord(rt.walk_done[b], a->stream);
+      rt.used[b] = true;
+      continue;
+    }
     const bool pool = (q.nfa || pa.pat.nfa_pair) && rt.kext.p;
     if (pool) {
       wa.kext = (uint64_t*)rt.kext.p;
@@ -2076,7 +2167,8 @@ int device_error(cep_app* a, unsigned int e) {
 int error_status(cep_app* a, unsigned int e) {
   if (!e) return CEP_OK;
   if (e & ERR_ORDER)   // root cause first: out-of-order input also defeats `within` pruning
-    return fail(a, CEP_E_ARG, "events not in event-time order: `within` requires non-decreasing timestamps");
+    return fail(a, CEP_E_ARG, "events not in event-time order: `within` requires non-decreasing timestamps "
+                              "(so does group by with #window.time outside a partition)");
   if (e & ERR_PENDING)
     return fail(a, CEP_E_CAPACITY, "per-key pending partial capacity exceeded (raise pending_slots)");
   if (e & ERR_POOL)
@@ -2170,16 +2262,24 @@ cep_app* cep::create_app(const char* plan, const cep_options* opt, const std::ve
   auto* a = new cep_app();
   if (opt) a->opt = *opt;
   else cep_default_options(&a->opt);
-  if (a->opt.pending_slots <= 0 || a->opt.pending_slots > kMaxPending) {
-    set_err(err, errlen, "pending_slots must be in [1, " + std::to_string(kMaxPending) + "]");
-    delete a;
-    return nullptr;
-  }
   if (a->opt.key_stride <= 0) a->opt.key_stride = 1;
   std::string m;
   int rc = compile_app(plan, &a->app, &m, dict_seed);
   if (rc) {
     set_err(err, errlen, m);
+    delete a;
+    return nullptr;
+  }
+  // pending_slots sizes the walks' LDS lists (kMaxPending); an app whose only
+  // per-key lists are #window.time rings (HBM) may ask for up to kWinMaxRing
+  bool has_pattern = false, has_window = false;
+  for (auto& q : a->app.queries) {
+    has_pattern |= q.kind == Q_PATTERN;
+    has_window |= q.win_kind != WIN_NONE;
+  }
+  const int max_pending = (has_window && !has_pattern) ? kWinMaxRing : kMaxPending;
+  if (a->opt.pending_slots <= 0 || a->opt.pending_slots > max_pending) {
+    set_err(err, errlen, "pending_slots must be in [1, " + std::to_string(max_pending) + "]");
     delete a;
     return nullptr;
   }
@@ -2969,6 +3069,13 @@ static uint64_t plan_hash(const CompiledApp& app) {
   };
   mix(app.code.data(), app.code.size() * sizeof(Ins));
   mix(app.konst.data(), app.konst.size() * 8);
+  // window kind and parameter (plans without a window hash as before)
+  for (size_t qi = 0; qi < app.queries.size(); ++qi) {
+    const Query& q = app.queries[qi];
+    if (q.win_kind == WIN_NONE) continue;
+    const int64_t w[4] = {(int64_t)qi, q.win_kind, q.win_param, q.win_global ? 1 : 0};
+    mix(w, sizeof(w));
+  }
   return h;
 }
 

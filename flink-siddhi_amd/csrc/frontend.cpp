@@ -8,7 +8,8 @@
 //   query      := 'from' input ['select' ('*' | item {',' item})]
 //                 ['group' 'by' attr {',' attr}] ['having' expr]
 //                 'insert' [('all'|'current'|'expired') 'events'] 'into' ID
-//   input      := ID {'[' expr ']'} ['as' ID]
+//   input      := ID {'[' expr ']'} [window] ['as' ID]
+//   window     := '#' 'window' '.' ('length' '(' INT ')' | 'time' '(' (INT | time) ')')
 //               | state ('->' state)* ['within' time]          (patterns)
 //   state      := ['every'] ID '=' ID ['[' expr ']']
 //   partition  := 'partition' 'with' '(' ID 'of' ID {',' ...} ')' 'begin' {query ';'} 'end'
@@ -199,6 +200,9 @@ struct QueryAst {
   bool sequence = false;
   std::string stream, alias;
   std::vector<ExprP> filters;
+  int win_kind = WIN_NONE;     // sliding window after the filters
+  int64_t win_param = 0;       // rows (length) / ms (time)
+  std::string win_events;      // window queries: the 'insert <x> events' keyword ("" = none given)
   std::vector<State> states;
   int64_t within = -1;
   bool select_all = true;
@@ -366,7 +370,11 @@ class Parser {
           q.filters.push_back(expr());
           expect(TK_OP, "]");
         } else if (peek().k == TK_OP && peek().v == "#") {
-          fail(CEP_E_UNSUPPORTED, "windows / stream functions are not supported");
+          if (q.win_kind != WIN_NONE)
+            fail(CEP_E_UNSUPPORTED, "a second window / stream function after #window is not supported");
+          window(&q);
+          if (peek().k == TK_OP && peek().v == "[")
+            fail(CEP_E_UNSUPPORTED, "a filter after the window (#window.x(..)[f]) is not supported");
         } else {
           break;
         }
@@ -421,12 +429,50 @@ class Parser {
     expect(TK_KW, "insert");
     if (peek().k == TK_KW &&
         (peek().v == "all" || peek().v == "current" || peek().v == "expired")) {
-      next();
+      const std::string ev = next().v;
       expect(TK_KW, "events");
+      // only a window has expired events: non-window queries emit the same
+      // rows whatever the keyword
+      if (q.win_kind != WIN_NONE) q.win_events = ev;
     }
     expect(TK_KW, "into");
     q.out = ident();
     return q;
+  }
+
+  // '#window.length(N)' / '#window.time(T)'; every other '#...' is refused.
+  void window(QueryAst* q) {
+    expect(TK_OP, "#");
+    Token t = next();
+    if (!(t.k == TK_KW && t.v == "window")) {
+      std::string name = t.v;
+      if (accept(TK_OP, ":")) name += ":" + next().v;
+      fail(CEP_E_UNSUPPORTED, "stream function #" + name + " is not supported");
+    }
+    expect(TK_OP, ".");
+    Token nt = next();
+    if (nt.k != TK_ID && nt.k != TK_KW) fail(CEP_E_PARSE, "window name expected after '#window.'");
+    const std::string name = nt.v;
+    if (name != "length" && name != "time")
+      fail(CEP_E_UNSUPPORTED, "#window." + name + " is not supported (only #window.length and #window.time)");
+    expect(TK_OP, "(");
+    int64_t v = -1;
+    if (peek().k == TK_NUM && peek(1).k == TK_OP && peek(1).v == ")") {
+      std::string n = next().v;
+      while (!n.empty() && (n.back() == 'l' || n.back() == 'L')) n.pop_back();
+      if (n.empty() || n.find_first_not_of("0123456789") != std::string::npos)
+        fail(CEP_E_PARSE, "#window." + name + " takes an integer constant, got " + n);
+      v = std::stoll(n);
+    } else if (name == "time" && peek().k == TK_NUM && peek(1).k == TK_ID) {
+      v = time_const();
+    } else {
+      fail(CEP_E_PARSE, "#window." + name + " takes one constant " +
+                            (name == "time" ? "time in ms or with units" : "row count") + ", got '" + peek().v + "'");
+    }
+    expect(TK_OP, ")");
+    if (v < 1) fail(CEP_E_PARSE, "#window." + name + " needs a constant >= 1");
+    q->win_kind = name == "length" ? WIN_LENGTH : WIN_TIME;
+    q->win_param = v;
   }
 
   int64_t time_const() {
@@ -455,6 +501,8 @@ class Parser {
       s.cond = expr();
       expect(TK_OP, "]");
     }
+    if (peek().k == TK_OP && peek().v == "#")
+      fail(CEP_E_UNSUPPORTED, "a window / stream function on a pattern or sequence state is not supported");
     if (accept(TK_OP, "+")) { s.min_count = 1; s.max_count = -1; }
     else if (accept(TK_OP, "*")) { s.min_count = 0; s.max_count = -1; }
     else if (accept(TK_OP, "?")) { s.min_count = 0; s.max_count = 1; }
@@ -1223,6 +1271,25 @@ void compile_single(CompiledApp* app, QueryAst& q) {
     out.group_cols.push_back(g->col);
   }
   bool agg = !out.aggs.empty();
+  if (q.win_kind != WIN_NONE) {
+    if (!q.win_events.empty() && q.win_events != "current")
+      fail(CEP_E_UNSUPPORTED, "insert " + q.win_events + " events on a window query is not supported "
+                                  "(only current events are emitted)");
+    // One window per key: the window instance and the aggregate group must
+    // coincide (partitioned, or no group by at all), or expiry must depend on
+    // the row's own ts only (group by + #window.time on ordered input, checked
+    // against cep_options.ts_order at cep_create).
+    if (agg && !q.partitioned && !q.group_by.empty() && q.win_kind == WIN_LENGTH)
+      fail(CEP_E_UNSUPPORTED, "a length window shared by several groups (#window.length with group by "
+                                  "outside a partition) is not supported");
+    // without an aggregate only current events reach the selector: the plain
+    // projection (the window holds no state anyone reads)
+    if (agg) {
+      out.win_kind = q.win_kind;
+      out.win_param = q.win_param;
+      out.win_global = !q.partitioned && !q.group_by.empty();
+    }
+  }
   // group by without aggregates: Siddhi's selector evaluates each event's
   // projection as it comes (no group state), so it is a plain projection; the
   // attributes still name the plan's routing keys (cep_plan_partition_keys)

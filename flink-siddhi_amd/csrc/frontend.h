@@ -5,7 +5,8 @@
 //   SiddhiCompiler.parse                 (SiddhiExecutionPlanner.java:76)
 //   SiddhiAppRuntime.getStreamDefinitionMap for output-type inference
 //                                         (SiddhiTypeFactory.java:64-112)
-// Unsupported-but-valid SiddhiQL (joins, windows, tables, extensions) fails
+// Unsupported-but-valid SiddhiQL (joins, windows other than sliding
+// #window.length / #window.time aggregates, tables, extensions) fails
 // with CEP_E_UNSUPPORTED so the Java shim can fall back to real Siddhi.
 #pragma once
 #include <map>
@@ -70,6 +71,13 @@ struct Query {
   std::vector<Prog> group_progs; // group-by expressions (host path when not a column)
   std::vector<int> group_cols;   // group-by attribute columns (routing keys)
   std::vector<AggSpec> aggs;
+  // sliding window in front of the aggregates (#window.length(N) / #window.time(T)):
+  // the engine keeps one window per key
+  int win_kind = WIN_NONE;
+  int64_t win_param = 0;         // rows (length) / ms (time)
+  bool win_global = false;       // Siddhi's window spans every group (group by without a
+                                 // partition): per-key windows are equivalent only for
+                                 // #window.time over non-decreasing ts (engine.cpp)
 
   // ---- 2-state pattern `[every] s1=A[f] -> s2=B[g] [within W]`
   int a_stream = -1, b_stream = -1;

@@ -267,6 +267,42 @@ struct WalkArgs {
   uint64_t pool_cap;           // slots per pool
 };
 
+// ------------------------------- sliding-window aggregates (win_kernels.hip) --
+// `from S[f]#window.length(N) | #window.time(T) select <aggregates> ...`: a
+// group-by query (pat.agg_mode = 1: records, key geometry, aggregates, having)
+// whose per-key state forgets.  One "slot" of pat.slot_words = nagg + ring *
+// entry_words words per key, in the WalkArgs layout (word w of key idx at
+// kslot[w * kstride + idx]):
+//   words [0, nagg)                      accumulator of aggregate j (sum: running sum, avg: running
+//                                        fp64 sum, min / max: extreme of the window, count: unused)
+//   word nagg + e * entry_words + v      ring entry e: value v (the carried record word val_word[v],
+//                                        one per distinct aggregate argument); time windows: the
+//                                        row's ts as the entry's last word
+//   khdr[idx] = 1 | head << 16 | count << 24   (0: the key has no state yet; head, count <= ring <= 255)
+// Every aggregate's row count is the window's count.
+constexpr int kWinMaxRing = 255;
+struct WinArgs {
+  VmArgs vm;
+  PatternArgs pat;
+  int32_t kind;                  // WIN_LENGTH / WIN_TIME
+  int64_t param;                 // rows / ms
+  int32_t ring;                  // entries per key: N (length), pending_slots (time)
+  int32_t nval;                  // distinct argument words per entry
+  int32_t entry_words;           // nval (+ 1: ts, time windows)
+  int32_t val_word[kMaxAggs];    // carried record word of entry value v
+  int32_t agg_val[kMaxAggs];     // entry value of aggregate j's argument (-1: count())
+  const uint64_t* recs;          // k_partition's output, unchanged
+  const uint16_t* tile_off;
+  int32_t ntiles;
+  int32_t tile_rows;
+  const int64_t* chunk_base;
+  uint32_t* khdr;
+  uint64_t* kslot;
+  int64_t kstride;
+  OutArgs out;
+  unsigned int* err;
+};
+
 // ------------------------------------------ closed-form fast path (cf_kernels.hip) --
 // `every s1=A[f] -> s2=B[g] within W` with f / g on the events' own columns,
 // at most 2 physical carried words per record and plain-copy select items.
@@ -642,6 +678,8 @@ void launch_route_rows(const RowRouteArgs& a, int64_t ntiles, uint32_t* toffs,
 void launch_unpack_rows(const RowUnpackArgs& a, hipStream_t s);
 void launch_cf_route(const CfRouteArgs& a, int64_t ntiles, hipStream_t s);
 void launch_walk(const WalkArgs& a, int nbuckets, bool vm, hipStream_t s);
+// sliding-window walk (win_kernels.hip); vm: having or computed select items
+void launch_winwalk(const WinArgs& a, int nbuckets, bool vm, hipStream_t s);
 // event-time reorder (reorder.hip)
 size_t reorder_temp_bytes(int64_t n);
 int reorder_sort(void* temp, size_t temp_bytes, const int64_t* keys_in, int64_t* keys_out, int32_t* idx_in,

@@ -98,6 +98,9 @@ constexpr int kMaxAggs = 8;
 constexpr int kMaxStates = 6;     // states of an N-state pattern / sequence
 enum AggFn { AGG_SUM = 0, AGG_COUNT = 1, AGG_AVG = 2, AGG_MIN = 3, AGG_MAX = 4 };
 
+// Sliding window of a group-by query (Query::win_kind, WinArgs::kind).
+enum WinKind : int32_t { WIN_NONE = 0, WIN_LENGTH = 1, WIN_TIME = 2 };
+
 // Role bits carried in partition records (pattern path).
 enum : uint32_t {
   ROLE_A = 1u,        // event passes the start state's filter f

@@ -55,7 +55,11 @@ class DuplicatedStreamException(SiddhiError):
 
 
 class UnsupportedPlanException(SiddhiError):
-    """Valid SiddhiQL outside the device subset (joins, windows, tables)."""
+    """Valid SiddhiQL outside the device subset: joins, tables, stream
+    functions, and every window but the sliding `#window.length(N)` /
+    `#window.time(T)` aggregates whose window instance is the aggregate group
+    (batch / external-time windows, a length window shared by several groups,
+    a filter after the window, expired-event output; include/cep.h)."""
     code = CEP_E_UNSUPPORTED
 
 

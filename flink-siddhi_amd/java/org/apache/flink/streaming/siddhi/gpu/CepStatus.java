@@ -10,8 +10,10 @@ final class CepStatus {
 
     private CepStatus() {}
 
-    /** Thrown for valid SiddhiQL outside the engine subset (joins, windows,
-     *  tables): the stream factory then builds the stock SiddhiStreamOperator. */
+    /** Thrown for valid SiddhiQL outside the engine subset (joins, tables,
+     *  windows other than sliding #window.length / #window.time aggregates
+     *  with one window per group): the stream factory then builds the stock
+     *  SiddhiStreamOperator. */
     static final class UnsupportedPlanException extends RuntimeException {
         UnsupportedPlanException(String msg) {
             super(msg);

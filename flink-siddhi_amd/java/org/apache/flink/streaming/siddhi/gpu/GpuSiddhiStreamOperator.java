@@ -64,7 +64,8 @@ import org.apache.flink.streaming.siddhi.schema.StreamSchema;
  * batch's matches when the batch is sent (batch full, watermark, checkpoint
  * barrier or close) instead of inside every send.
  *
- * A plan outside the engine subset (joins, windows, tables) throws
+ * A plan outside the engine subset (joins, tables, windows other than
+ * sliding #window.length / #window.time aggregates, include/cep.h) throws
  * CepStatus.UnsupportedPlanException from the constructor, so a factory can
  * build the stock SiddhiStreamOperator instead:
  * <pre>

@@ -24,6 +24,24 @@
  * and valid only during the callback.  Snapshot buffers are engine-allocated
  * and released with cep_free().
  *
+ * Window queries: a single-stream query may put one sliding window after its
+ * filter, `from S[f]#window.length(N) ...` (N rows, 1 <= N <= 255) or
+ * `from S[f]#window.time(T) ...` (T in ms or with units, >= 1; the clock is
+ * the event ts), with the select list, group by, having and `insert [current
+ * events] into` of the plain group-by query.  Per kept row: expired rows leave
+ * the aggregates oldest first (length: the oldest when the window is full;
+ * time: front rows with ts + T <= the row's ts, positionally, in any ts
+ * order), then the row is added and one output row is emitted (upstream Siddhi
+ * 4.x semantics).  The engine keeps one window per key, so the
+ * window instance and the aggregate group must coincide: inside `partition
+ * with` (group by absent or the partition key), or with no partition and no
+ * group by (one global window).  `group by k` + #window.time outside a
+ * partition is accepted with ts_order = 1 only (cep_create: CEP_E_UNSUPPORTED
+ * otherwise); `group by k` + #window.length outside a partition, a filter
+ * after the window, every other #window.x / stream function, `insert expired /
+ * all events` and windows on pattern states or joins are CEP_E_UNSUPPORTED.
+ * A window query without aggregates is the plain projection.
+ *
  * Hot-key probe: a keyed `every A -> B` runtime on the closed-form path
  * walks its first 2^20 rows as a short chunk and waits for it once inside
  * that cep_send_batch() (its hot-key verdict decides the next chunk's
@@ -48,8 +66,9 @@ extern "C" {
  *                              SiddhiOperatorContext.java:151)
  *   CEP_E_DUPLICATED_STREAM-> exception/DuplicatedStreamException.java:20
  *   CEP_E_UNSUPPORTED      -> valid SiddhiQL outside the engine subset
- *                             (joins, windows, tables): shim falls back to
- *                             real Siddhi
+ *                             (joins, tables, windows other than the sliding
+ *                             #window.length / #window.time aggregates
+ *                             below): shim falls back to real Siddhi
  *   CEP_E_ARG              -> IllegalArgumentException
  *                             (operator/StreamOutputHandler.java:89)
  *   CEP_E_DEVICE           -> HIP failure / no gfx950 device
@@ -86,7 +105,12 @@ typedef struct {
 
 typedef struct cep_options {
   int32_t device;          /* HIP device ordinal (default 0) */
-  int32_t pending_slots;   /* per-key pending partial matches (default 16) */
+  int32_t pending_slots;   /* per-key pending partial matches (default 16, at most 16).
+                              Also the rows a #window.time ring holds per key: a window
+                              that needs more live rows for a key fails the next cep_flush
+                              with CEP_E_CAPACITY (rows past pending_slots do not spill to
+                              the pending pool).  An app whose only per-key lists are such
+                              rings (no pattern / sequence) may ask for up to 255. */
   int64_t key_capacity;    /* partition / group keys are ints in [0, key_capacity) (default 1<<20) */
   int64_t chunk_events;    /* events per device chunk (default 1<<22) */
   int32_t buckets_log2;    /* key buckets per chunk, log2 (default 10) */
