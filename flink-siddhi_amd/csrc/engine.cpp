@@ -181,6 +181,7 @@ struct MqRT {
   int32_t ncond[8] = {0};
   uint32_t stream_mask = 0;
   int key_col = -1;
+  int view = -1;                         // query chaining: the view its queries read (-1: the batch)
   std::vector<int> carry;                // logical carried columns
   std::vector<int> cond_cols;            // columns the conditions read
   bool check_order = false;
@@ -239,6 +240,12 @@ struct cep_app {
   DevBuf ostats;               // cep_flush: per output {~min seq, max seq, descents} (k_seq_stats)
   DevBuf okeys[2], oidx[2], otemp;   // cep_flush: emission-order sort scratch (shared by the outputs)
   DevBuf rr_col[kMaxCols], rr_ts, rr_stream, rr_seq;   // cep_send_rows: unpacked rows
+  // query chaining: per view (CompiledApp::views) and stage, the handle column
+  // and the materialised columns of the last batch (stateless: rebuilt per batch)
+  struct ViewStage {
+    DevBuf stream, col[kMaxCols];
+  };
+  std::vector<std::vector<ViewStage>> views;
   // host batches: two staging slots (pinned host arena + device arena); a
   // batch's H2D copy runs on the copy stream while the previous batch's
   // kernels run on the main stream
@@ -511,6 +518,7 @@ struct MqClassB {
   int kind = MQU_SEQ;
   std::string sig;
   int key_col = -1, layout = -1;
+  int view = -1;
   std::vector<int> qs;
   std::vector<MqNeeds> nds;
 };
@@ -519,7 +527,7 @@ struct MqClassB {
 // (sequence classes advance bit-parallel, aggregations share the decode).
 std::string mq_signature(const cep_app* a, const Query& q, const MqNeeds& nd, int* kind) {
   const CompiledApp& app = a->app;
-  std::string sg = std::to_string(nd.key_col) + "/" + std::to_string(nd.layout) + "|";
+  std::string sg = std::to_string(nd.key_col) + "/" + std::to_string(nd.layout) + "/" + std::to_string(q.view) + "|";
   auto add = [&](int64_t v) { sg += std::to_string(v) + ","; };
   const auto& od = app.outputs[app.output_index(q.out_stream)];
   for (auto& at : od.attrs) add(at.type);
@@ -636,6 +644,7 @@ int build_mq_groups(cep_app* a) {
       c->sig = sig;
       c->key_col = nd.key_col;
       c->layout = nd.layout;
+      c->view = app.queries[qi].view;
     }
     c->qs.push_back((int)qi);
     c->nds.push_back(nd);
@@ -669,10 +678,13 @@ int build_mq_groups(cep_app* a) {
     };
     int gi = -1;
     for (size_t i = 0; i < a->mqs.size() && gi < 0; ++i)
-      if (a->mqs[i].key_col == c.key_col && same_layout(app, layouts[i], c.layout) && fits(a->mqs[i])) gi = (int)i;
+      if (a->mqs[i].key_col == c.key_col && a->mqs[i].view == c.view && same_layout(app, layouts[i], c.layout) &&
+          fits(a->mqs[i]))
+        gi = (int)i;
     if (gi < 0) {
       MqRT g;
       g.key_col = c.key_col;
+      g.view = c.view;
       g.conds.resize(8 * kMqMaxCond);
       if (!fits(g)) {
         if (c.qs.size() > 1) {   // halve the class and place both halves
@@ -2121,15 +2133,156 @@ int run_mq(cep_app* a, MqRT& g, const RowsArgs& rows_all) {
   return CEP_OK;
 }
 
-int send_device_rows(cep_app* a, const RowsArgs& rows) {
+// Query chaining: view `vi` of the slice (derive.hip).  One k_derive launch
+// per chain depth; stage k reads stage k-1's view.  The view keeps the
+// slice's n, ts, arrival numbers and row positions; its handle column and
+// the columns that are not same-position plain copies are the app's buffers,
+// laid out so that row0 has the alignment a 256-byte-aligned caller column
+// has there (run_filter's pair-load test and pref_aligned decide as for the
+// batch itself).  A stage none of whose producers can see a row of the slice
+// (no handle column, another input) is skipped.
+int build_view(cep_app* a, int vi, const RowsArgs& rows, RowsArgs* out) {
+  const CompiledApp& app = a->app;
+  const View& v = app.views[vi];
+  if (a->views.size() < app.views.size()) a->views.resize(app.views.size());
+  auto& stages = a->views[vi];
+  if ((int)stages.size() < v.stages) stages.resize(v.stages);
+  RowsArgs cur = rows;
+  for (int st = 1; st <= v.stages; ++st) {
+    DeriveArgs da{};
+    bool seen = cur.stream != nullptr;
+    for (int di : v.derived) {
+      const Derived& d = app.derived[di];
+      if (d.stage != st) continue;
+      // a slice of another layout holds no row of this producer's source (a
+      // mixed batch mixes identical definitions); its columns are not the
+      // ones the producer's programs index
+      const auto& sa = app.inputs[d.source].attrs;
+      bool same = (int)sa.size() == cur.cols.n;
+      for (int c = 0; same && c < cur.cols.n; ++c) same = sa[c].type == cur.cols.t[c];
+      if (!same) continue;
+      seen = seen || d.source == cur.input;
+      const Query& q = app.queries[d.producer];
+      DeriveProd& p = da.prod[da.nprod++];
+      p.src = d.source;
+      p.dst = d.stream;
+      p.filter_prog = q.filter.off;
+      p.terms = q.filter_terms;
+      for (size_t c = 0; c < q.select.size(); ++c) {
+        p.item_src[c] = q.select[c].src;
+        p.item_prog[c] = q.select[c].prog.off;
+      }
+      da.ncols = (int)q.select.size();
+      for (int c = 0; c < da.ncols; ++c) da.out_type[c] = q.select[c].type;
+    }
+    if (!seen || da.nprod == 0) continue;
+    auto& bufs = stages[st - 1];
+    // a caller column p is 256-byte aligned: p + row0 * w sits at (row0 * w) % 256
+    auto place = [&](DevBuf* b, int w) -> char* {
+      const size_t pad = (size_t)((cur.row0 * w) & 255);
+      if (!dev_ensure(b, pad + (size_t)cur.n * w + 256, a->stream, false)) return nullptr;
+      return (char*)b->p + pad - cur.row0 * w;
+    };
+    da.rows = cur;
+    da.vm = {(const Ins*)a->code.p, (const uint64_t*)a->konst.p};
+    da.err = (unsigned int*)a->err.p;
+    da.stream_out = (uint8_t*)place(&bufs.stream, 1);
+    if (!da.stream_out) return fail(a, CEP_E_DEVICE, "out of device memory (view)");
+    // columns the term-list instance loads once per row
+    bool vm = false, wide = false;
+    da.npref = 0;
+    for (int c = 0; c < kMaxCols; ++c) da.col_slot[c] = -1;
+    auto slot_of = [&](int col) {
+      for (int k = 0; k < da.npref; ++k)
+        if (da.pcol[k] == col) return k;
+      if (da.npref == kDerivePref) {
+        wide = true;
+        return 0;
+      }
+      da.pcol[da.npref] = col;
+      da.col_slot[col] = da.npref;
+      return da.npref++;
+    };
+    // a program the interpreter runs: every column it loads is prefetched
+    auto prog_cols = [&](int off) {
+      vm = true;
+      for (int pc = off; pc >= 0 && pc < (int)app.code.size() && app.code[pc].op != OP_END; ++pc)
+        if (app.code[pc].op == OP_LDCOL) slot_of((int)app.code[pc].imm);
+    };
+    for (int i = 0; i < da.nprod; ++i) {
+      DeriveProd& p = da.prod[i];
+      if (p.filter_prog >= 0 && p.terms.n < 0) prog_cols(p.filter_prog);
+      for (int t = 0; t < std::max(0, p.terms.n); ++t) p.fslot[t] = slot_of(p.terms.t[t].col);
+    }
+    for (int c = 0; c < da.ncols; ++c) {
+      bool alias = c < cur.cols.n && cur.cols.t[c] == da.out_type[c];
+      for (int i = 0; i < da.nprod; ++i) alias = alias && da.prod[i].item_src[c] == SRC_REC + c;
+      da.own_col[c] = (c < cur.cols.n && cur.cols.t[c] == da.out_type[c]) ? c : -1;
+      da.own_slot[c] = -1;
+      if (alias) continue;
+      da.col_out[c] = place(&bufs.col[c], type_width(da.out_type[c]));
+      if (!da.col_out[c]) return fail(a, CEP_E_DEVICE, "out of device memory (view)");
+      if (da.own_col[c] >= 0) da.own_slot[c] = slot_of(da.own_col[c]);
+      for (int i = 0; i < da.nprod; ++i) {
+        const int src = da.prod[i].item_src[c];
+        if (src >= SRC_REC && src < SRC_TS) da.prod[i].item_slot[c] = slot_of(src - SRC_REC);
+        else prog_cols(da.prod[i].item_prog[c]);
+      }
+    }
+    for (int k = da.npref; k < kDerivePref; ++k) da.pcol[k] = da.npref ? da.pcol[0] : 0;
+    auto al = [&](const void* ptr, int w) {
+      return (((uintptr_t)ptr + (uintptr_t)(cur.row0 * w)) & (uintptr_t)(w == 1 ? 7 : 15)) == 0;
+    };
+    bool vec = al(da.stream_out, 1) && (cur.stream ? al(cur.stream, 1) : true);
+    for (int k = 0; k < da.npref; ++k) vec = vec && al(cur.cols.p[da.pcol[k]], type_width(cur.cols.t[da.pcol[k]]));
+    for (int c = 0; c < da.ncols; ++c)
+      if (da.col_out[c]) vec = vec && al(da.col_out[c], type_width(da.out_type[c]));
+    da.vec = vec ? 1 : 0;
+    {
+      LaunchTimer t(a, CEP_K_OTHER);
+      launch_derive(da, vm, wide, a->stream);
+    }
+    RowsArgs nx = cur;
+    nx.stream = da.stream_out;
+    nx.cols.n = da.ncols;
+    for (int c = 0; c < da.ncols; ++c) {
+      nx.cols.t[c] = da.out_type[c];
+      nx.cols.p[c] = da.col_out[c] ? da.col_out[c] : cur.cols.p[c];
+    }
+    cur = nx;
+  }
+  *out = cur;
+  return CEP_OK;
+}
+
+int send_device_rows(cep_app* a, const RowsArgs& rows_in) {
+  // query chaining: each view is built once per slice, before its first reader
+  std::vector<RowsArgs> views(a->app.views.size());
+  std::vector<char> built(a->app.views.size(), 0);
+  auto rows_of = [&](int view, const RowsArgs** r) -> int {
+    *r = &rows_in;
+    if (view < 0) return CEP_OK;
+    if (!built[view]) {
+      const int rc = build_view(a, view, rows_in, &views[view]);
+      if (rc) return rc;
+      built[view] = 1;
+    }
+    *r = &views[view];
+    return CEP_OK;
+  };
   for (auto& g : a->mqs) {
-    const int rc = run_mq(a, g, rows);
+    const RowsArgs* r;
+    int rc = rows_of(g.view, &r);
+    if (!rc) rc = run_mq(a, g, *r);
     if (rc) return rc;
   }
   for (size_t qi = 0; qi < a->app.queries.size(); ++qi) {
     const Query& q = a->app.queries[qi];
     if (a->in_mq[qi]) continue;
-    int rc = CEP_OK;
+    const RowsArgs* rp;
+    int rc = rows_of(q.view, &rp);
+    if (rc) return rc;
+    const RowsArgs& rows = *rp;
     if (q.kind == Q_FILTER) {
       rc = run_filter(a, q, rows);
     } else if (q.kind == Q_PATTERN || q.kind == Q_AGG) {
@@ -2140,6 +2293,7 @@ int send_device_rows(cep_app* a, const RowsArgs& rows) {
   }
   // the batch's last ts: the next batch's first-row order check (device
   // batches; the host does not see their ts)
+  const RowsArgs& rows = rows_in;
   if (rows.n > 0 && rows.prev_ts_dev)
     hipMemcpyAsync(a->last_ts_dev.p, rows.ts + rows.row0 + rows.n - 1, 8, hipMemcpyDeviceToDevice, a->stream);
   return CEP_OK;
@@ -2182,6 +2336,9 @@ int error_status(cep_app* a, unsigned int e) {
                 "padded key shuffle: an owner's records overflowed the padded segment (seg_cap) and, with "
                 "a spill buffer, the spill (spill_cap) too; the excess records were dropped (raise seg_cap / "
                 "spill_cap or use the two-phase exchange)");
+  if (e & ERR_DERIVE)
+    return fail(a, CEP_E_UNSUPPORTED, "a row passed the filters of two derived streams that one query reads "
+                                      "(it would be two events of that query; make the producers' filters disjoint)");
   if (e & ERR_TS_SPAN)
     return fail(a, CEP_E_ARG, "timestamps of one chunk lie more than 2^31 ms apart (lower chunk_events)");
   if (e & ERR_OUT_CAP) return fail(a, CEP_E_DEVICE, "output capacity exceeded");
@@ -2499,6 +2656,11 @@ void cep_destroy(cep_app* a) {
   dev_free(&a->str_hash);
   host_free(&a->flush_words);
   for (auto& d : a->rr_col) dev_free(&d);
+  for (auto& v : a->views)
+    for (auto& st : v) {
+      dev_free(&st.stream);
+      for (auto& d : st.col) dev_free(&d);
+    }
   dev_free(&a->rr_ts);
   dev_free(&a->rr_stream);
   dev_free(&a->rr_seq);
@@ -3076,6 +3238,17 @@ static uint64_t plan_hash(const CompiledApp& app) {
     const int64_t w[4] = {(int64_t)qi, q.win_kind, q.win_param, q.win_global ? 1 : 0};
     mix(w, sizeof(w));
   }
+  // query chaining (plans without derived streams hash as before)
+  for (auto& d : app.derived) {
+    const int64_t w[5] = {-1, d.stream, d.producer, d.source, d.stage};
+    mix(w, sizeof(w));
+  }
+  for (size_t qi = 0; qi < app.queries.size(); ++qi) {
+    if (app.queries[qi].view < 0) continue;
+    const int64_t w[3] = {-2, (int64_t)qi, app.queries[qi].view};
+    mix(w, sizeof(w));
+    for (int di : app.views[app.queries[qi].view].derived) mix(&di, sizeof(di));
+  }
   return h;
 }
 
@@ -3447,6 +3620,9 @@ static int route_batch(cep_app* a, const cep_batch* b, int world, int64_t seq0, 
                        int64_t rec_cap, int64_t* counts_host, int64_t seg_cap, const SpillArgs& sp = SpillArgs()) {
   if (!a || !b || world <= 0 || (seg_cap == 0 && !counts_host) || seg_cap < 0) return CEP_E_ARG;
   if (world > kMaxWorld) return fail(a, CEP_E_ARG, "world exceeds " + std::to_string(kMaxWorld));
+  if (!a->app.derived.empty())
+    return fail(a, CEP_E_UNSUPPORTED, "key shuffle of an app with query chaining (derived streams) is not supported: "
+                                      "the sender needs the key in source columns");
   if (a->pats.size() != 1 || a->app.queries.size() != 1)
     return fail(a, CEP_E_UNSUPPORTED, "key shuffle needs an app with exactly one keyed pattern");
   PatternRT& rt = a->pats[0];
@@ -3702,6 +3878,9 @@ static int route_rows(cep_app* a, const cep_batch* b, int world, int64_t seq0, v
                       int64_t* counts_host, int64_t seg_cap, const SpillArgs& sp = SpillArgs()) {
   if (!a || !b || world <= 0 || seg_cap < 0 || (seg_cap == 0 && !counts_host)) return CEP_E_ARG;
   if (world > kMaxWorld) return fail(a, CEP_E_ARG, "world exceeds " + std::to_string(kMaxWorld));
+  if (!a->app.derived.empty())
+    return fail(a, CEP_E_UNSUPPORTED, "row shuffle of an app with query chaining (derived streams) is not supported: "
+                                      "the sender needs the key in source columns");
   int32_t kc[8];
   int layout;
   int rc = row_route_plan(a, kc, &layout);
@@ -3883,26 +4062,42 @@ int cep_plan_partition_keys(const char* plan, const char* stream_id, char* buf, 
   // incompatible partitions.  Extension: the reference's planner rejects
   // `partition with` blocks; here a partitioned query names its partition
   // attribute of the stream.
+  // Query chaining: a keyed query on a derived stream M needs the rows of one
+  // key on one operator instance just as well, so its key on M, followed back
+  // through plain-copy select items to an attribute of this stream, counts as
+  // a key of this stream (the reference's planner looks at each query's own
+  // input only and cannot see this).  A computed key names nothing.
   const auto& attrs = app.inputs[in].attrs;
   std::vector<int> keys;
   for (auto& q : app.queries) {
-    std::vector<int> k;
-    if (q.in_stream == in) {
-      k = q.group_cols;
-      if (k.empty() && q.part_col >= 0) k.push_back(q.part_col);
-    } else if (q.nfa) {
-      if (in < (int)q.key_col_s.size() && q.key_col_s[in] >= 0) k.push_back(q.key_col_s[in]);
-    } else if (q.a_stream == in || q.b_stream == in) {
-      const int c = q.a_stream == in ? q.key_col_a : q.key_col_b;
-      if (c >= 0) k.push_back(c);
+    for (int s : query_streams(q)) {
+      std::vector<int> k;
+      if (q.in_stream == s) {
+        k = q.group_cols;
+        if (k.empty() && q.part_col >= 0) k.push_back(q.part_col);
+      } else if (q.nfa) {
+        if (s < (int)q.key_col_s.size() && q.key_col_s[s] >= 0) k.push_back(q.key_col_s[s]);
+      } else if (q.a_stream == s || q.b_stream == s) {
+        const int c = q.a_stream == s ? q.key_col_a : q.key_col_b;
+        if (c >= 0) k.push_back(c);
+      }
+      if (s != in) {   // a derived stream of this one: translate, or nothing
+        std::vector<int> t;
+        for (int c : k) {
+          int ss = s, cc = c;
+          if (source_column(app, &ss, &cc) && ss == in) t.push_back(cc);
+        }
+        if (t.size() != k.size()) t.clear();
+        k = t;
+      }
+      if (k.empty()) continue;
+      if (!keys.empty() && keys != k) {
+        std::snprintf(buf, len, "incompatible partitions on stream %s: [%s] vs [%s]", stream_id,
+                      attrs[keys[0]].name.c_str(), attrs[k[0]].name.c_str());
+        return CEP_E_PARSE;
+      }
+      keys = k;
     }
-    if (k.empty()) continue;
-    if (!keys.empty() && keys != k) {
-      std::snprintf(buf, len, "incompatible partitions on stream %s: [%s] vs [%s]", stream_id,
-                    attrs[keys[0]].name.c_str(), attrs[k[0]].name.c_str());
-      return CEP_E_PARSE;
-    }
-    keys = k;
   }
   std::string s;
   for (int c : keys) {

@@ -362,6 +362,8 @@ class Parser {
   QueryAst query() {
     expect(TK_KW, "from");
     QueryAst q;
+    if (peek().k == TK_OP && peek().v == "#")
+      fail(CEP_E_UNSUPPORTED, "inner streams (from #" + peek(1).v + ") are not supported");
     if (!is_state_start()) {
       q.single = true;
       q.stream = ident();
@@ -436,6 +438,8 @@ class Parser {
       if (q.win_kind != WIN_NONE) q.win_events = ev;
     }
     expect(TK_KW, "into");
+    if (peek().k == TK_OP && peek().v == "#")
+      fail(CEP_E_UNSUPPORTED, "inner streams (insert into #" + peek(1).v + ") are not supported");
     q.out = ident();
     return q;
   }
@@ -496,6 +500,8 @@ class Parser {
     s.every = accept(TK_KW, "every");
     s.alias = ident();
     expect(TK_OP, "=");
+    if (peek().k == TK_OP && peek().v == "#")
+      fail(CEP_E_UNSUPPORTED, "inner streams (" + s.alias + "=#" + peek(1).v + ") are not supported");
     s.stream = ident();
     if (accept(TK_OP, "[")) {
       s.cond = expr();
@@ -1092,8 +1098,24 @@ void add_output(CompiledApp* app, const std::string& id, const std::vector<OutIt
   StreamSchema od;
   od.id = id;
   for (auto& it : items) od.attrs.push_back({it.name, it.type});
-  if (app->input_index(id) >= 0)
-    fail(CEP_E_UNSUPPORTED, "inserting into an input stream (query chaining) is not supported");
+  auto same_def = [&](const StreamSchema& prev) {
+    bool same = prev.attrs.size() == od.attrs.size();
+    for (size_t i = 0; same && i < od.attrs.size(); ++i)
+      same = prev.attrs[i].name == od.attrs[i].name && prev.attrs[i].type == od.attrs[i].type;
+    return same;
+  };
+  // query chaining: `insert into M` defines M for the queries after it; a
+  // `define stream M` must say the same.  M takes an input handle only when
+  // some query reads it (resolve_chains decides what that means).
+  const int in = app->input_index(id);
+  if (in >= 0 && !same_def(app->inputs[in]))
+    fail(CEP_E_PARSE, "incompatible definitions for stream " + id +
+                          ": the select list does not match its earlier definition");
+  if (in < 0 && std::find(app->read_ids.begin(), app->read_ids.end(), id) != app->read_ids.end()) {
+    if (app->inputs.size() >= 31) fail(CEP_E_UNSUPPORTED, "more than 31 input and derived streams");
+    StreamSchema sd = od;
+    app->inputs.push_back(sd);
+  }
   int k = app->output_index(id);
   if (k >= 0) {
     const auto& prev = app->outputs[k];
@@ -1201,6 +1223,7 @@ void compile_single(CompiledApp* app, QueryAst& q) {
   Query out;
   out.in_stream = si;
   out.out_stream = q.out;
+  out.in_partition = q.partitioned;
   Ctx c;
   c.mode = Ctx::SINGLE;
   c.single = &sd;
@@ -1390,6 +1413,7 @@ void compile_nfa(CompiledApp* app, QueryAst& q) {
   out.nfa = true;
   out.sequence = q.sequence;
   out.out_stream = q.out;
+  out.in_partition = q.partitioned;
   out.every = q.states[0].every;
   out.within = q.within;
   out.a_stream = app->input_index(q.states[0].stream);
@@ -1533,6 +1557,7 @@ void compile_pattern(CompiledApp* app, QueryAst& q) {
   out.kind = Q_PATTERN;
   out.out_stream = q.out;
   out.a_stream = app->input_index(q.states[0].stream);
+  out.in_partition = q.partitioned;
   out.b_stream = app->input_index(q.states[1].stream);
   out.every = q.states[0].every;
   out.within = q.within;
@@ -1651,7 +1676,147 @@ void compile_pattern(CompiledApp* app, QueryAst& q) {
   app->queries.push_back(out);
 }
 
+bool same_types(const StreamSchema& x, const StreamSchema& y) {
+  if (x.attrs.size() != y.attrs.size()) return false;
+  for (size_t c = 0; c < x.attrs.size(); ++c)
+    if (x.attrs[c].type != y.attrs[c].type) return false;
+  return true;
+}
+
+// Query chaining.  A query whose output stream some query reads is a producer;
+// the streams it feeds are derived.  Checks what the engine's views cannot do
+// and records, per query, the producers behind the derived streams it reads.
+void resolve_chains(CompiledApp* app) {
+  const int ni = (int)app->inputs.size();
+  std::vector<char> read(ni, 0);
+  for (auto& q : app->queries)
+    for (int s : query_streams(q)) read[s] = 1;
+  for (size_t qi = 0; qi < app->queries.size(); ++qi) {
+    const Query& q = app->queries[qi];
+    const int m = app->input_index(q.out_stream);
+    if (m < 0 || !read[m]) continue;   // an output nobody reads
+    const std::string what = "stream " + q.out_stream + " is read by another query: its producer ";
+    if (q.kind == Q_PATTERN)
+      fail(CEP_E_UNSUPPORTED, what + "must be a plain filter / projection query, not a pattern or sequence");
+    if (q.win_kind != WIN_NONE)
+      fail(CEP_E_UNSUPPORTED, what + "must be a plain filter / projection query, not a window query");
+    if (q.kind == Q_AGG)
+      fail(CEP_E_UNSUPPORTED, what + "must be a plain filter / projection query, not an aggregate query");
+    if (q.having.valid())
+      fail(CEP_E_UNSUPPORTED, what + "must be a plain filter / projection query, without having");
+    if (q.in_partition)
+      fail(CEP_E_UNSUPPORTED, what + "inside a partition block is not supported");
+    app->derived.push_back({m, (int)qi, q.in_stream, 0});
+  }
+  if (app->derived.empty()) return;
+  // depth of every stream (raw inputs 0); a stream still open when reached
+  // again closes a cycle
+  std::vector<int> depth(ni, -1), open(ni, 0);
+  std::function<int(int)> depth_of = [&](int s) -> int {
+    if (depth[s] >= 0) return depth[s];
+    if (open[s]) fail(CEP_E_UNSUPPORTED, "cycle of queries through stream " + app->inputs[s].id + " is not supported");
+    open[s] = 1;
+    int d = 0;
+    for (auto& p : app->derived)
+      if (p.stream == s) d = std::max(d, 1 + depth_of(p.source));
+    open[s] = 0;
+    return depth[s] = d;
+  };
+  int nderived = 0;
+  for (int s = 0; s < ni; ++s) {
+    if (depth_of(s) > kMaxChainDepth)
+      fail(CEP_E_UNSUPPORTED, "query chain deeper than 4 (stream " + app->inputs[s].id + ")");
+    nderived += depth[s] > 0;
+  }
+  if (nderived > kMaxDerived) fail(CEP_E_UNSUPPORTED, "more than 8 derived streams");
+  // row records carry the handle in a few bits and the pattern kernels index
+  // per-handle tables of 8 (kernels.h PatternArgs::key_col_s)
+  if (ni > 8) fail(CEP_E_UNSUPPORTED, "query chaining over more than 8 defined and derived streams");
+  for (auto& p : app->derived) p.stage = depth[p.source] + 1;
+  // per query: every derived stream behind the ones it reads
+  for (auto& q : app->queries) {
+    const std::vector<int> reads = query_streams(q);
+    std::vector<char> anc(ni, 0);   // streams some read stream derives from
+    std::function<void(int)> up = [&](int s) {
+      for (auto& p : app->derived)
+        if (p.stream == s && !anc[p.source]) {
+          anc[p.source] = 1;
+          up(p.source);
+        }
+    };
+    bool any = false;
+    for (int s : reads)
+      if (depth[s] > 0) {
+        any = true;
+        up(s);
+      }
+    if (!any) continue;
+    for (int s : reads)
+      if (anc[s])
+        fail(CEP_E_UNSUPPORTED, "one query reading a derived stream and stream " + app->inputs[s].id +
+                                    " it derives from (a row would be two events of the query) is not supported");
+    for (int s : reads)
+      if (!same_types(app->inputs[s], app->inputs[reads[0]]))
+        fail(CEP_E_UNSUPPORTED, "a query reading derived streams needs identical definitions of every stream it "
+                                "reads (" + app->inputs[s].id + " differs from " + app->inputs[reads[0]].id + ")");
+    View v;
+    for (int st = 1; st <= kMaxChainDepth; ++st) {
+      int n = 0, first = -1;
+      for (size_t di = 0; di < app->derived.size(); ++di) {
+        const Derived& p = app->derived[di];
+        const bool wanted = anc[p.stream] || std::find(reads.begin(), reads.end(), p.stream) != reads.end();
+        if (p.stage != st || !wanted) continue;
+        if (first >= 0 && !same_types(app->inputs[p.stream], app->inputs[first]))
+          fail(CEP_E_UNSUPPORTED, "derived streams " + app->inputs[p.stream].id + " and " + app->inputs[first].id +
+                                      " feed one query at the same chain depth and need identical definitions");
+        first = p.stream;
+        v.derived.push_back((int)di);
+        v.stages = st;
+        if (++n > kMaxStageProducers)
+          fail(CEP_E_UNSUPPORTED, "more than 4 producers at one chain depth behind one query");
+      }
+    }
+    for (size_t vi = 0; vi < app->views.size() && q.view < 0; ++vi)
+      if (app->views[vi].derived == v.derived) q.view = (int)vi;
+    if (q.view < 0) {
+      app->views.push_back(v);
+      q.view = (int)app->views.size() - 1;
+    }
+  }
+}
+
 }  // namespace
+
+std::vector<int> query_streams(const Query& q) {
+  std::vector<int> out;
+  auto mark = [&](int s) {
+    if (s >= 0 && std::find(out.begin(), out.end(), s) == out.end()) out.push_back(s);
+  };
+  if (q.nfa) {
+    for (auto& st : q.nstates) mark(st.stream);
+  } else {
+    mark(q.in_stream);
+    mark(q.a_stream);
+    mark(q.b_stream);
+  }
+  return out;
+}
+
+bool source_column(const CompiledApp& app, int* stream, int* col) {
+  for (int hop = 0; hop <= kMaxChainDepth && app.is_derived(*stream); ++hop) {
+    const Derived* only = nullptr;
+    for (auto& d : app.derived)
+      if (d.stream == *stream) {
+        if (only) return false;
+        only = &d;
+      }
+    const OutItem& it = app.queries[only->producer].select[*col];
+    if (it.src < SRC_REC || it.src >= SRC_TS) return false;
+    *stream = only->source;
+    *col = it.src - SRC_REC;
+  }
+  return !app.is_derived(*stream);
+}
 
 std::vector<int> read_inputs(const CompiledApp& app) {
   std::vector<char> used(app.inputs.size(), 0);
@@ -1678,9 +1843,14 @@ int compile_app(const std::string& text, CompiledApp* out, std::string* err,
     std::vector<QueryAst> qs;
     Parser(text).parse(&app.inputs, &qs);
     for (auto& q : qs) {
+      if (q.single) app.read_ids.push_back(q.stream);
+      for (auto& st : q.states) app.read_ids.push_back(st.stream);
+    }
+    for (auto& q : qs) {
       if (q.single) compile_single(&app, q);
       else compile_pattern(&app, q);
     }
+    resolve_chains(&app);
     *out = std::move(app);
     return CEP_OK;
   } catch (const CepError& e) {

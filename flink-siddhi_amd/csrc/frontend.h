@@ -111,7 +111,33 @@ struct Query {
   std::vector<NState> nstates;
   std::vector<NCap> ncaps;
   std::vector<int> key_col_s;    // per input stream handle: partition key column (-1)
+
+  // ---- query chaining (derive.hip): the query reads derived streams through
+  // view `view` of CompiledApp::views (-1: it reads the batch as sent)
+  int view = -1;
+  bool in_partition = false;     // written inside a `partition with` block
 };
+
+// A producer of a derived stream: a plain filter / projection query whose
+// output stream some query reads.  Its rows reach the readers as a masked
+// view of the batch (engine.cpp build_view), not through its OutStream.
+struct Derived {
+  int stream;      // input handle of the derived stream
+  int producer;    // query index
+  int source;      // input handle the producer reads
+  int stage;       // 1 + depth of the source (raw inputs: depth 0)
+};
+
+// The derived streams one query (or several) reads: every producer behind
+// them, in stage order.  Stage k's producers read stage k-1's view.
+struct View {
+  std::vector<int> derived;      // indices into CompiledApp::derived, stage order
+  int stages = 0;
+};
+
+constexpr int kMaxChainDepth = 4;
+constexpr int kMaxDerived = 8;
+constexpr int kMaxStageProducers = 4;   // producers sharing one k_derive pass
 
 struct CompiledApp {
   std::vector<StreamSchema> inputs;     // defined input streams
@@ -120,11 +146,19 @@ struct CompiledApp {
   std::vector<Ins> code;
   std::vector<uint64_t> konst;
   std::vector<std::string> strings;     // string literals (dictionary order)
+  std::vector<Derived> derived;         // query chaining: producers of read derived streams
+  std::vector<View> views;
+  std::vector<std::string> read_ids;    // stream ids the plan's queries read (compile_app)
 
   int input_index(const std::string& id) const {
     for (size_t i = 0; i < inputs.size(); ++i)
       if (inputs[i].id == id) return (int)i;
     return -1;
+  }
+  bool is_derived(int handle) const {
+    for (auto& d : derived)
+      if (d.stream == handle) return true;
+    return false;
   }
   int output_index(const std::string& id) const {
     for (size_t i = 0; i < outputs.size(); ++i)
@@ -153,5 +187,13 @@ const char* type_name(int t);
 // Input streams some query reads (InputStream.getUniqueStreamIds over the
 // plan's queries), in definition order.
 std::vector<int> read_inputs(const CompiledApp& app);
+
+// Input handles one query reads.
+std::vector<int> query_streams(const Query& q);
+
+// Query chaining: the attribute of raw input `*stream` that column `*col` of a
+// derived stream is a plain copy of, through every producer on the way
+// (false: some producer computes it, or the stream has several producers).
+bool source_column(const CompiledApp& app, int* stream, int* col);
 
 }  // namespace cep

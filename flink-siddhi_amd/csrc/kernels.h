@@ -69,6 +69,7 @@ enum : uint32_t {
   ERR_KEYMAP = 64u,          // more distinct partition values than key_capacity (sparse keys)
   ERR_TS_SPAN = 128u,        // a chunk's ts lie more than 2^31 ms either side of its first row
   ERR_SHUFFLE_CAP = 256u,    // padded key shuffle: an owner segment held more than seg_cap records
+  ERR_DERIVE = 512u,         // query chaining: a row passed the filters of two derived streams one query reads
 };
 
 // Per-key state header: pending count (bits 0-7, <= S) | started << 8 |
@@ -649,6 +650,49 @@ struct MqWalkArgs {
   int32_t ablate;                 // diagnostics (CEP_MQ_ABLATE): 1 = rows counted, not stored
   unsigned int* err;
 };
+
+// --------------------------------------------- query chaining (derive.hip) --
+// One stage of a view: the slice's rows relabelled with the handles of the
+// derived streams their producers put them on, and the select items that are
+// not plain same-position copies materialised into dense columns indexed
+// like the batch.  Everything else of the view aliases the slice.
+constexpr int kDeriveProds = 4;     // producers sharing one pass
+constexpr int kDerivePref = 6;      // distinct columns the term-list instance loads
+constexpr int kDeriveThreads = 256;
+constexpr int kDeriveRows = 8;      // consecutive rows per lane
+struct DeriveProd {
+  int32_t src, dst;                 // handle read / handle given to passing rows
+  int32_t filter_prog;              // -1: every row of src passes
+  TermList terms;                   // n >= 0: interpreter-free filter
+  int32_t fslot[kMaxTerms];         // term-list instance: loaded slot of each term's column
+  int32_t item_src[kMaxCols];       // per output position: SRC_REC + c (copy of column c) or SRC_VM
+  int32_t item_prog[kMaxCols];
+  int32_t item_slot[kMaxCols];      // term-list instance: loaded slot of the copied column
+};
+struct DeriveArgs {
+  RowsArgs rows;
+  VmArgs vm;
+  int32_t nprod;
+  DeriveProd prod[kDeriveProds];
+  uint8_t* stream_out;              // indexed like the batch (row0 + i)
+  int32_t ncols;                    // columns of the derived definition
+  void* col_out[kMaxCols];          // nullptr: the position aliases the slice's column
+  int32_t out_type[kMaxCols];
+  int32_t own_col[kMaxCols];        // rows that stay: the slice's column at this position when its
+                                    // type is out_type (else -1: zero)
+  int32_t own_slot[kMaxCols];       // term-list instance: its loaded slot
+  int32_t npref;                    // term-list instance: loaded columns
+  int32_t pcol[kDerivePref];
+  int32_t col_slot[kMaxCols];       // interpreter over prefetched rows: loaded slot of column c (-1)
+  int32_t vec;                      // every loaded column, the handle column and every output is
+                                    // aligned for the vector path at row0 (else: row by row)
+  unsigned int* err;
+};
+// vm: some filter or select item needs the interpreter; rowwise: more than
+// kDerivePref distinct columns are read.  Aligned slices (a.vec) that are not
+// rowwise run k_derive_vec over a.npref prefetched columns, the others the
+// row-by-row kernel.
+void launch_derive(const DeriveArgs& a, bool vm, bool rowwise, hipStream_t s);
 
 // --------------------------------------------------------------- launchers --
 void launch_mq_partition(const MqPartArgs& a, hipStream_t s);

@@ -226,8 +226,11 @@ int cep_plan_input_streams(const char* plan, char* buf, size_t len) {
     std::snprintf(buf, len, "%s", m.c_str());
     return rc;
   }
+  // query chaining: a derived stream is fed by its producer inside the plan,
+  // not from outside (rows may still be sent to it, cep_input)
   std::string s;
   for (int i : read_inputs(app)) {
+    if (app.is_derived(i)) continue;
     if (!s.empty()) s += '\n';
     s += app.inputs[i].id;
   }

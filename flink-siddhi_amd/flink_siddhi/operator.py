@@ -105,7 +105,9 @@ def stream_definition_expression(stream_id: str, attrs: Sequence[Tuple[str, str]
 
 def plan_input_streams(plan: str) -> List[str]:
     """Input streams the plan's queries read (the router's
-    inputStreamToExecutionPlans, router/AddRouteOperator.java:159-175)."""
+    inputStreamToExecutionPlans, router/AddRouteOperator.java:159-175).
+    Streams the plan derives itself (query chaining: some query of the plan
+    inserts into them) are left out: only what must be fed from outside."""
     buf = C.create_string_buffer(4096)
     rc = L.lib().cep_plan_input_streams(plan.encode(), buf, len(buf))
     L.raise_for(rc, buf.value.decode())
@@ -115,7 +117,9 @@ def plan_input_streams(plan: str) -> List[str]:
 
 def plan_partition_keys(plan: str, stream_id: str) -> List[str]:
     """The group-by attributes that partition `stream_id` for `plan`
-    (SiddhiExecutionPlanner.getStreamPartitions, utils/SiddhiExecutionPlanner.java:76-140)."""
+    (SiddhiExecutionPlanner.getStreamPartitions, utils/SiddhiExecutionPlanner.java:76-140).
+    A keyed query on a stream derived from `stream_id` counts too when its key
+    is a plain copy of an attribute of `stream_id` (a computed key names none)."""
     buf = C.create_string_buffer(4096)
     rc = L.lib().cep_plan_partition_keys(plan.encode(), stream_id.encode(), buf, len(buf))
     L.raise_for(rc, buf.value.decode())

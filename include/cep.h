@@ -236,7 +236,26 @@ int cep_plan_schema(const char* plan, const char* stream_id, cep_attr* out,
 /* ---- runtime ----------------------------------------------------------- */
 
 /* SiddhiManager.createSiddhiAppRuntime(plan) + start()
- * — AbstractSiddhiOperator.java:120-122,137-142.  NULL on error. */
+ * — AbstractSiddhiOperator.java:120-122,137-142.  NULL on error.
+ *
+ * Query chaining.  A query may read a stream an earlier query inserts into:
+ * `insert into M` defines M with the select list's names and types (a `define
+ * stream M` must agree, CEP_E_PARSE otherwise; reading M before any
+ * definition is CEP_E_UNDEFINED_STREAM).  Delivery is synchronous: M's
+ * events carry the ts and the arrival number of the source row, a reader
+ * sees all its streams merged in arrival order, and its rows carry the ts and
+ * arrival number of the source row that completed them.  M stays an ordinary
+ * output (callbacks, cep_flush).  Producers are plain filter / projection
+ * queries outside `partition`, chained at most 4 deep; a chained plan holds
+ * at most 8 streams with a handle, defined and derived together (two defined
+ * streams leave room for six derived ones); every query kind may read them.
+ * Other producers, inner streams (#M), cycles, and one query reading a
+ * derived stream together with a stream it derives from are
+ * CEP_E_UNSUPPORTED at cep_validate; so are
+ * cep_route_batch* / cep_route_rows* on such an app.  A source row that
+ * passes the filters of two derived streams which one query reads would be
+ * two events of that query: the next cep_flush fails with CEP_E_UNSUPPORTED
+ * (disjoint filters work).  Parity with Siddhi is unpinned. */
 cep_app* cep_create(const char* plan, const cep_options* opt, char* err,
                     size_t errlen);
 
@@ -248,7 +267,11 @@ int cep_stream_schema(cep_app* app, const char* stream_id, cep_attr* out,
                       int cap, int* n);
 
 /* getInputHandler(id) — AbstractSiddhiOperator.java:172.
- * Returns a handle >= 0, or -CEP_E_UNDEFINED_STREAM. */
+ * Returns a handle >= 0, or -CEP_E_UNDEFINED_STREAM.  A derived stream that
+ * some query reads (query chaining, cep_create) is an input too: its handle
+ * follows the defined streams', and rows sent to it reach its readers like
+ * any input's, interleaved by arrival with the rows its producer derives.
+ * An output stream no query reads has no handle. */
 int cep_input(cep_app* app, const char* stream_id);
 
 /* addCallback(outId, StreamCallback) — AbstractSiddhiOperator.java:165-166 */
