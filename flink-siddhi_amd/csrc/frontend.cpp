@@ -1098,6 +1098,9 @@ void add_output(CompiledApp* app, const std::string& id, const std::vector<OutIt
   StreamSchema od;
   od.id = id;
   for (auto& it : items) od.attrs.push_back({it.name, it.type});
+  // the kernels' output descriptors hold kMaxCols columns (OutArgs, DeriveArgs)
+  if ((int)items.size() > kMaxCols)
+    fail(CEP_E_UNSUPPORTED, "more than " + std::to_string(kMaxCols) + " attributes in the select list of " + id);
   auto same_def = [&](const StreamSchema& prev) {
     bool same = prev.attrs.size() == od.attrs.size();
     for (size_t i = 0; same && i < od.attrs.size(); ++i)

@@ -66,6 +66,21 @@ def _f32(x: float) -> float:
         return math.copysign(math.inf, x)
 
 
+def _int_to_f32(v: int) -> float:
+    """(float) of an int / long: one rounding to 24 bits, ties to even
+    (JLS 5.1.2).  Going through binary64 first rounds twice:
+    2^62 + 2^38 + 1 would land on 2^62 instead of the float above it."""
+    a = abs(v)
+    sh = a.bit_length() - 24
+    if sh > 0:
+        q, r = a >> sh, a & ((1 << sh) - 1)
+        half = 1 << (sh - 1)
+        if r > half or (r == half and (q & 1)):
+            q += 1
+        a = q << sh
+    return float(-a if v < 0 else a)
+
+
 def _java_idiv(a: int, b: int) -> int:
     q = abs(a) // abs(b)
     return q if (a >= 0) == (b >= 0) else -q
@@ -815,7 +830,7 @@ def _convert(v, frm: str, to: str):
     if to == LONG:
         return int(v)
     if to == FLOAT:
-        return _f32(float(v))
+        return _int_to_f32(v) if frm in (INT, LONG) else _f32(float(v))
     if to == DOUBLE:
         return float(v)
     return v

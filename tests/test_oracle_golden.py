@@ -167,6 +167,17 @@ def test_appA2_null_compare_is_false():
     assert len(rt.send("S", 0, (1, 1))) == 1
 
 
+def test_long_to_float_rounds_once():
+    # JLS 5.1.2: (float) long rounds once.  2^62 + 2^38 + 1 is above the tie
+    # between 2^62 and the next float, but rounding to binary64 first drops
+    # the + 1, and the tie then goes to even (2^62): `l > f` failed in error
+    plan = "define stream S (l long, f float);from S[l > f] select l insert into O;"
+    rt = O.OracleRuntime(plan)
+    v = (1 << 62) + (1 << 38) + 1
+    assert [e.data for e in rt.send("S", 0, (v, 2.0 ** 62))] == [(v,)]
+    assert rt.send("S", 1, (v - 1, 2.0 ** 62)) == []       # the exact tie: to even
+
+
 def test_appA6_running_aggregates_group_by_having():
     plan = ("define stream S (k int, p double);"
             "from S select k, sum(p) as total, count() as n group by k having total > 1.0 "
