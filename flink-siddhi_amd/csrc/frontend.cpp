@@ -1208,7 +1208,7 @@ void lower_aggregation(CompiledApp* app, Query& q) {
     a.arg_type = a.arg.valid() ? app->code[a.arg.off].b : T_LONG;
   }
   for (auto& it : q.select) {
-    const Ins& in = app->code[it.prog.off];
+    const Ins in = app->code[it.prog.off];   // a copy: remap_cols grows app->code
     const bool single = it.prog.len == 2 && in.dst == 0;
     it.prog = remap_cols(app, it.prog, cols);
     it.src = SRC_VM;

@@ -1722,11 +1722,17 @@ __global__ __launch_bounds__(kWalkThreads) void k_walk(WalkArgs a) {
   WALK_STAMP(1);
 
   int t0 = 0;
+  // A tile's segment can hold more than a window of this bucket (up to
+  // tile_rows = 2048 records: few groups, dense input).  Its records are not
+  // in arrival order, so it is split by arrival number: one window takes the
+  // kWalkWindow earliest records (those up to `pivot`), the next one the rest.
+  bool half = false;     // tile t0's records up to `pivot` are done
+  uint32_t pivot = 0;
   while (t0 < ntiles) {
     if (tid == 0) {
-      // largest t1 with seg[t1] - seg[t0] <= window (a single tile's segment is
-      // at most tile_rows = 2048 > window: such a tile is split below)
-      int lo = t0 + 1, hi = ntiles;
+      // largest t1 with seg[t1] - seg[t0] <= window; a half-done tile is
+      // finished on its own
+      int lo = t0 + 1, hi = half ? t0 + 1 : ntiles;
       const uint32_t lim = Lseg[t0] + kWalkWindow;
       while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -1740,16 +1746,53 @@ __global__ __launch_bounds__(kWalkThreads) void k_walk(WalkArgs a) {
     const int t1 = (int)L.t1;
     const uint32_t wbase = Lseg[t0];
     const uint32_t nrec = Lseg[t1] - wbase;
-    if (nrec > kWalkWindow) {   // one tile holds more than a window of this bucket
-      set_err(a.err, ERR_WINDOW);
-    }
-    const uint32_t nw = nrec < (uint32_t)kWalkWindow ? nrec : (uint32_t)kWalkWindow;
-    // gather the window: record indices per tile segment (LDS only), then one
-    // independent 16-byte header load (+ carried words) per record
-    for (int t = t0 + tid; t < t1; t += kWalkThreads) {
-      const uint32_t pos = Lseg[t] - wbase, cnt = Lseg[t + 1] - Lseg[t];
-      const uint32_t g0 = (uint32_t)t * (uint32_t)a.tile_rows + Llo[t];
-      for (uint32_t j = 0; j < cnt && pos + j < (uint32_t)kWalkWindow; ++j) L.wrec[pos + j] = g0 + j;
+    const bool split = half || nrec > (uint32_t)kWalkWindow;   // (then t1 == t0 + 1)
+    uint32_t nw = nrec;
+    if (!split) {
+      // gather the window: record indices per tile segment (LDS only), then one
+      // independent 16-byte header load (+ carried words) per record
+      for (int t = t0 + tid; t < t1; t += kWalkThreads) {
+        const uint32_t pos = Lseg[t] - wbase, cnt = Lseg[t + 1] - Lseg[t];
+        const uint32_t g0 = (uint32_t)t * (uint32_t)a.tile_rows + Llo[t];
+        for (uint32_t j = 0; j < cnt && pos + j < (uint32_t)kWalkWindow; ++j) L.wrec[pos + j] = g0 + j;
+      }
+    } else {
+      const uint32_t g0 = (uint32_t)t0 * (uint32_t)a.tile_rows + Llo[t0];
+      auto arrival = [&](uint32_t j) { return (uint32_t)a.recs[(int64_t)(g0 + j) * rw + 1]; };
+      if (!half) {
+        // the smallest pivot with kWalkWindow arrival numbers up to it (they
+        // are distinct, so exactly kWalkWindow), searched between the
+        // segment's smallest and largest arrival number: a tile's rows are
+        // consecutive, so about 11 steps
+        if (tid == 0) {
+          L.scratch[10] = 0xffffffffu;
+          L.scratch[11] = 0u;
+        }
+        lds_barrier();
+        for (uint32_t j = tid; j < nrec; j += kWalkThreads) {
+          const uint32_t s = arrival(j);
+          atomicMin(&L.scratch[10], s);
+          atomicMax(&L.scratch[11], s);
+        }
+        lds_barrier();
+        uint32_t lo = L.scratch[10], hi = L.scratch[11];
+        while (lo < hi) {
+          const uint32_t mid = lo + ((hi - lo) >> 1);
+          uint32_t c = 0, total;
+          for (uint32_t j = tid; j < nrec; j += kWalkThreads) c += arrival(j) <= mid ? 1u : 0u;
+          block_excl_scan(c, L.scratch, &total);
+          if (total >= (uint32_t)kWalkWindow) hi = mid;
+          else lo = mid + 1;
+        }
+        pivot = lo;
+      }
+      uint32_t c = 0, total;
+      for (uint32_t j = tid; j < nrec; j += kWalkThreads) c += ((arrival(j) <= pivot) != half) ? 1u : 0u;
+      uint32_t off = block_excl_scan(c, L.scratch, &total);
+      if (total > (uint32_t)kWalkWindow) set_err(a.err, ERR_WINDOW);   // (a segment of more than two windows)
+      nw = total < (uint32_t)kWalkWindow ? total : (uint32_t)kWalkWindow;
+      for (uint32_t j = tid; j < nrec; j += kWalkThreads)
+        if (((arrival(j) <= pivot) != half) && off < (uint32_t)kWalkWindow) L.wrec[off++] = g0 + j;
     }
     lds_barrier();
     for (uint32_t w = tid; w < nw; w += kWalkThreads) {
@@ -2026,8 +2069,14 @@ __global__ __launch_bounds__(kWalkThreads) void k_walk(WalkArgs a) {
     }
     // the next window re-reads state slots this one wrote (HBM) and reuses
     // the LDS arrays: full barrier; none after the last window
-    if (t1 < ntiles) __syncthreads();
-    t0 = t1;
+    const bool again = split && !half;   // the rest of tile t0 comes next
+    if (again || t1 < ntiles) __syncthreads();
+    if (again) {
+      half = true;
+    } else {
+      t0 = t1;
+      half = false;
+    }
   }
   if constexpr (kVm)
     if (p.nfa_mode && a.kext) nfa_settle_runs(a, L, bucket, kpb);
