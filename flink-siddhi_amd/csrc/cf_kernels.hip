@@ -81,6 +81,11 @@ constexpr int kCfStageBytes = (kCfTile / 8192 * 20 + 36) * 1024;    // a tile ke
       atomicAdd((unsigned long long*)&a.stamps[4095 * 16 + (i)], (unsigned long long)(v));   \
   } while (0)
 
+// The walk's diagnostics exist only in instances compiled with them (DIAG).
+#define CFW_STAMP(i) do { if constexpr (DIAG) CF_STAMP(i); } while (0)
+#define CFW_WSTAMP(slot) do { if constexpr (DIAG) CF_WSTAMP(slot); } while (0)
+#define CFW_COUNT(i, v) do { if constexpr (DIAG) CF_COUNT(i, v); } while (0)
+
 // Carried word of each row: slot sa on A rows (role_a bit set), sb otherwise;
 // both slots uniform.
 template <int E, int Q = kPref>
@@ -701,6 +706,83 @@ __device__ __forceinline__ void cf_emit(const CfWalkArgs& a, unsigned long long 
   if (a.out.write_seq) a.out.seq[pos] = seq;
 }
 
+// What a walk instance is compiled for (k_cfwalk's FL), all known on the host
+// before the launch (launch_cf_walk); an instance without a feature holds no
+// code, no registers and no argument loads for it.
+constexpr int kWfDiag = 1;    // stamps, ablations, event counters (CEP_STAMPS / CEP_ABLATE)
+constexpr int kWfSeq = 2;     // received records whose output stores seq (in_seq)
+constexpr int kWfHot = 4;     // hot-key diversion is on (hot_id): diverted keys are not the walk's
+constexpr int kWfAll = 7;
+
+// ---- overflow runs: a pending list longer than the S inline slots keeps
+// slots [S, n) in a run of the pending pool.  A key finds out mid-bucket, so
+// every instance handles it, but the walk keeps neither the run offset nor
+// the pool pointers in registers across windows: the run's place lives in
+// the key's kext word, count | offset << 32, offset bit 31 (kOvoWr) = the
+// run is already in this launch's write pool (cleared again by
+// cf_ovf_finish; the host keeps pool offsets below 2^31).  (Inlined: as
+// __noinline__ calls these cost the caller more spills than they save.)
+constexpr uint32_t kOvoWr = 0x80000000u;
+constexpr uint32_t kNoOff = 0xffffffffu;
+
+// word `word` of the key's run (slot j word w: (j - S) * slot_words + w)
+__device__ __forceinline__ uint64_t* cf_ovf_ptr(const uint64_t* pool_rd, uint64_t* pool_wr, const uint64_t* kx,
+                                             int sw, int64_t word) {
+  const uint32_t ovo = (uint32_t)(*kx >> 32);
+  uint64_t* run = ((ovo & kOvoWr) ? pool_wr : (uint64_t*)pool_rd) + (uint64_t)(ovo & ~kOvoWr) * (uint64_t)sw;
+  return run + word;
+}
+__device__ __forceinline__ uint64_t cf_ovf_word(const uint64_t* pool_rd, uint64_t* pool_wr, const uint64_t* kx,
+                                             int sw, int64_t word) {
+  return *cf_ovf_ptr(pool_rd, pool_wr, kx, sw, word);
+}
+// a fresh run of cnt slots in the write pool (kNoOff: the pool is full, ERR_POOL set)
+__device__ __forceinline__ uint32_t cf_ovf_alloc(unsigned long long* cursor, uint64_t pool_cap, unsigned int* err,
+                                              uint32_t cnt) {
+  const unsigned long long o = atomicAdd(cursor, (unsigned long long)cnt);
+  if (o + cnt > pool_cap) {
+    set_err(err, ERR_POOL);
+    return kNoOff;
+  }
+  return (uint32_t)o;
+}
+// slot idx of the fresh run noff
+__device__ __forceinline__ void cf_ovf_put(uint64_t* pool_wr, uint32_t noff, int idx, int sw, uint64_t ts,
+                                        uint64_t x0, uint64_t x1) {
+  uint64_t* o = pool_wr + ((uint64_t)noff + (uint64_t)idx) * (uint64_t)sw;
+  o[0] = ts;
+  if (sw > 2) o[2] = x0;
+  if (sw > 3) o[3] = x1;
+}
+// the list was rebuilt with its tail in the fresh run noff
+__device__ __forceinline__ void cf_ovf_commit(uint64_t* kx, int n, uint32_t noff) {
+  *kx = (uint64_t)(uint32_t)n | ((uint64_t)(noff | kOvoWr) << 32);
+}
+// kernel end: a run still in the read pool moves to the write pool (the read
+// pool is the next launch's write pool); kext takes its final form.  Returns
+// whether the run moved.
+__device__ __forceinline__ bool cf_ovf_finish(const uint64_t* pool_rd, uint64_t* pool_wr, unsigned long long* cursor,
+                                           uint64_t pool_cap, unsigned int* err, uint64_t* kx, int n, int S,
+                                           int sw) {
+  uint32_t ovo = (uint32_t)(*kx >> 32);
+  bool moved = false;
+  if (!(ovo & kOvoWr)) {
+    const unsigned long long cnt = (unsigned long long)(n - S);
+    const unsigned long long off = atomicAdd(cursor, cnt);
+    if (off + cnt > pool_cap) {
+      set_err(err, ERR_POOL);
+    } else {
+      uint64_t* o = pool_wr + off * (uint64_t)sw;
+      const uint64_t* src = pool_rd + (uint64_t)ovo * (uint64_t)sw;
+      for (int64_t i = 0; i < (int64_t)cnt * sw; ++i) o[i] = src[i];
+      ovo = (uint32_t)off;
+      moved = true;
+    }
+  }
+  *kx = (uint64_t)(uint32_t)n | ((uint64_t)(ovo & ~kOvoWr) << 32);
+  return moved;
+}
+
 }  // namespace
 
 // NC: captured words per pending slot (slot_words - 2); TOL: order-tolerant
@@ -712,12 +794,14 @@ __device__ __forceinline__ void cf_emit(const CfWalkArgs& a, unsigned long long 
 // latest g-failing B row is more than W after are dropped (App. A.3: in an
 // in-order chunk that row expires every partial any of the chunk's g-failing
 // B rows expires, and none that a g-passing B would still complete)
-template <int NW, bool KR, int NC, bool TOL = false, bool ATL = false>
-__global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   // 2 workgroups per CU
+// FL: the features the body is compiled for (kWf*)
+template <int NW, bool KR, int NC, bool TOL, bool ATL, int FL>
+__device__ __forceinline__ void cf_walk_body(const CfWalkArgs& a, CfWalkLds<NW>& L) {
   constexpr int NT = kCfWalkThreads, RW = 1 + NW, WIN = cf_window<NW>();
   constexpr int TPT = kCfMaxTiles / NT;   // tiles per thread
   constexpr int PER = WIN / NT;           // window slots per thread
-  __shared__ CfWalkLds<NW> L;
+  constexpr bool DIAG = (FL & kWfDiag) != 0, SEQ = (FL & kWfSeq) != 0, HOT = (FL & kWfHot) != 0;
+  const int ablate = DIAG ? a.ablate : 0;
   const int tid = threadIdx.x;
   const PatternArgs& p = a.pat;
   const int lg = p.buckets_log2;
@@ -733,12 +817,13 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
   // fallback of an in-order chunk has nothing to do (uniform: one word)
   if (ATL && *(volatile const uint32_t*)a.gate == a.gate_seq) return;
   if (TOL && a.gate && *(volatile const uint32_t*)a.gate != a.gate_seq) return;
-  CF_STAMP(0);
+  CFW_STAMP(0);
 
   // ---- key lane (tid < kpb): pending count + slots 0 / 1 in registers,
   // loaded now so the state read overlaps the gather below.  A hot key's
   // records were diverted to the hot path this launch: its state is not ours.
-  const bool klane = tid < kpb && !(a.hot_id && a.hot_id[((int64_t)tid << lg) | bucket] != kNotHot);
+  bool klane = tid < kpb;
+  if constexpr (HOT) klane = klane && !(a.hot_id && a.hot_id[((int64_t)tid << lg) | bucket] != kNotHot);
   uint32_t kcnt = 0;   // the key's records this launch (hot-key candidates)
   const int64_t kidx = (int64_t)bucket * kpb + tid;
   // slot j word w of this key at byte kb + (j * sw + w) * pb of kslot: 32-bit
@@ -756,15 +841,13 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
   // overflow run of the pending pool: header bit kHdrOvf set, kext = n |
   // run offset << 32 in this launch's read pool.  Runs are rewritten into the
   // write pool whenever the list is rebuilt (and moved there at kernel end
-  // otherwise): the host swaps the two pools per launch.  The run lives in
-  // one register: ovo = offset | kOvoWr (run in the write pool); the host
-  // keeps pool offsets below 2^31.
+  // otherwise): the host swaps the two pools per launch.  Where the run is
+  // stays in kext during the launch (cf_ovf_*): the walk holds only the list
+  // length n.
   const bool ovf0 = klane && (hdr & kHdrOvf);
   const uint64_t ext0 = ovf0 ? a.kext[kidx] : 0ull;
-  uint32_t ovo = (uint32_t)(ext0 >> 32);
-  constexpr uint32_t kOvoWr = 0x80000000u;
-  auto ovp = [&]() -> const uint64_t* {
-    return ((ovo & kOvoWr) ? a.pool_wr : a.pool_rd) + (uint64_t)(ovo & ~kOvoWr) * (uint64_t)sw;
+  auto ovf_word = [&](int j, int w) -> uint64_t {   // slot j >= S
+    return cf_ovf_word(a.pool_rd, a.pool_wr, a.kext + kidx, sw, (int64_t)(j - S) * sw + w);
   };
   // bucket-major offset table, loaded before the slot loads below (those
   // wait for hdr; these need not)
@@ -825,7 +908,7 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
   uint32_t pcb = 0;
   auto slot_word = [&](int j, int w) -> uint64_t {
     if (j >= 2) {
-      if (j >= S) return ovp()[(int64_t)(j - S) * sw + w];
+      if (j >= S) return ovf_word(j, w);
       if (j - 2 < cn) return L.pcache[pcb + (uint32_t)((j - 2) * cw + (w == 0 ? 0 : w - 1))];
       return sl_ld(j, w);
     }
@@ -863,7 +946,7 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
     if (tid == 0) L.seg[ntiles] = total;
   }
   lds_barrier();
-  CF_STAMP(1);
+  CFW_STAMP(1);
   const uint32_t nall = L.seg[ntiles];
   // ATL: each key lane's latest g-failing B row so far (dts + 1, 0: none),
   // raised window by window from the expiry entries of the bucket's twin
@@ -993,8 +1076,8 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
       L.khasa[tid] = 0;
     }
     lds_barrier();
-    if (wi == 1) CF_STAMP(9);   // window 1: the window's record table is built
-    if (ATL && !(a.ablate & 16)) {   // (ablate 16, diagnostics: no expiry entries)
+    if (wi == 1) CFW_STAMP(9);   // window 1: the window's record table is built
+    if (ATL && !(ablate & 16)) {   // (ablate 16, diagnostics: no expiry entries)
       // this window's tiles; an oversize tile's entries with its last piece
       // (a row of it past the piece may follow a g-passing B of the next one)
       const int tz = over ? (piece + nw >= L.seg[t0 + 1] - L.seg[t0] ? t0 + 1 : t0) : t1;
@@ -1026,7 +1109,7 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
       if (q < nw) atomicAdd(&L.kstart[kbuf][hk[i] + 1], 1u);
     }
     lds_barrier();
-    CF_STAMP(wi * 8 + 2);
+    CFW_STAMP(wi * 8 + 2);
     // ---- counting sort by key of (seq, key, slot) entries, then each entry's
     // arrival rank inside its key run -> sorted position of window slot q
     {
@@ -1072,7 +1155,7 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
         L.sseq[s] = hs[i];
         // received records: global arrival number - chunk base (read only
         // when the output stores seq: a scattered load per record)
-        if (a.in_seq && a.out.write_seq)
+        if (SEQ && a.in_seq && a.out.write_seq)
           L.sseq[s] = (uint32_t)((int64_t)a.in_seq[(int64_t)hs[i] * a.in_rec_words] - seq_base);
         L.skr[s] = (uint16_t)(rec_key(w0) | (rec_role(w0) << 12));
         if (NW > 0) L.scap[0][s] = ((uint64_t)x[i].w << 32) | x[i].z;
@@ -1080,7 +1163,7 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
       }
     }
     lds_barrier();
-    CF_STAMP(wi * 8 + 3);
+    CFW_STAMP(wi * 8 + 3);
     // ---- key lanes: slots >= 2 of the pending list -> pcache (wrec is dead
     // from here to the next window).  The first two are loaded now and
     // written after the position scan below, so their latency is hidden; a
@@ -1312,7 +1395,7 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
       }
     }
     lds_barrier();
-    CF_STAMP(wi * 8 + 4);
+    CFW_STAMP(wi * 8 + 4);
 
     // ---- match flag per sorted position (+ carried matches at run start);
     // one scan yields both the output offsets (low 20 bits) and each record
@@ -1384,13 +1467,13 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
         L.base = rows ? atomicAdd(a.out.count, (unsigned long long)rows) : 0ull;
         L.nrec = total >> 20;
       }
-      if (tid == 0) { CF_COUNT(1, rows); CF_COUNT(5, 1); }
+      if (tid == 0) { CFW_COUNT(1, rows); CFW_COUNT(5, 1); }
     }
     lds_barrier();
 #ifndef CF_WAVESTAMP
-    CF_STAMP(wi * 8 + 5);
+    CFW_STAMP(wi * 8 + 5);
 #else
-    if ((threadIdx.x >> 6) == 0) CF_WSTAMP(0);
+    if ((threadIdx.x >> 6) == 0) CFW_WSTAMP(0);
 #endif
     const unsigned long long base = L.base;
     const int cp0 = a.cf.cap_phys[0], cp1 = a.cf.cap_phys[1];
@@ -1403,10 +1486,10 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
       const int64_t kl = ((int64_t)tid << lg) | bucket;
       const int64_t kv = kl * p.key_stride + p.key_offset;
       const uint16_t fb = L.kfb[tid], lb = L.klb[tid];
-      CF_COUNT(7, 1);
-      if (n > 2) CF_COUNT(2, 1);
+      CFW_COUNT(7, 1);
+      if (n > 2) CFW_COUNT(2, 1);
       if (cm) {
-        CF_COUNT(0, cm);
+        CFW_COUNT(0, cm);
         const int64_t bts = ts_base + (int64_t)L.sts[fb];
         const uint64_t b0 = NW > 0 ? L.scap[0][fb] : 0ull, b1 = NW > 1 ? L.scap[NW > 1 ? 1 : 0][fb] : 0ull;
         if (TOL || ATL) {   // the carried partials that survived to the first B, in slot order
@@ -1440,17 +1523,10 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
       const uint32_t from = (lb == kNoB ? r0 : (uint32_t)lb);
       int cap = (lb == kNoB ? n : 0) + (int)(r1 - from);
       // the new overflow run: pool_wr slot noff on (kNoOff: none / pool full)
-      constexpr uint32_t kNoOff = 0xffffffffu;
       uint32_t noff = kNoOff;
       if (cap > S) {
-        const unsigned long long cnt = (unsigned long long)(cap - S);
-        const unsigned long long o = atomicAdd(a.pool_cursor, cnt);
-        if (o + cnt > a.pool_cap) {
-          set_err(a.err, ERR_POOL);
-          cap = S;
-        } else {
-          noff = (uint32_t)o;
-        }
+        noff = cf_ovf_alloc(a.pool_cursor, a.pool_cap, a.err, (uint32_t)(cap - S));
+        if (noff == kNoOff) cap = S;
       }
       auto put_slot = [&](uint64_t ts, uint64_t x0, uint64_t x1) {
         const uint64_t m0 = 0ull - (uint64_t)(nn == 0), m1 = 0ull - (uint64_t)(nn == 1);
@@ -1460,16 +1536,13 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
         t1r = (ts & m1) | (t1r & ~m1);
         a1c0 = (x0 & m1) | (a1c0 & ~m1);
         a1c1 = (x1 & m1) | (a1c1 & ~m1);
-        if (nn >= 2) CF_COUNT(4, 1);
+        if (nn >= 2) CFW_COUNT(4, 1);
         if (nn >= S) {   // overflow run
           if (noff == kNoOff) {   // the pool ran out (ERR_POOL set): keep the device safe
             ++nn;
             return;
           }
-          uint64_t* o = a.pool_wr + ((uint64_t)noff + (uint64_t)(nn - S)) * (uint64_t)sw;
-          o[0] = ts;
-          if (c1) o[2] = x0;
-          if (c2) o[3] = x1;
+          cf_ovf_put(a.pool_wr, noff, nn - S, sw, ts, x0, x1);
         } else if (nn >= 2) {   // slots 0 / 1 are stored once, at kernel end
           sl_st(nn, 0, ts);
           if (c1) sl_st(nn, 2, x0);
@@ -1478,7 +1551,7 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
         ++nn;
         dirty = true;
       };
-      if (lb == kNoB && (a.ablate & 1)) {
+      if (lb == kNoB && (ablate & 1)) {
         nn = 0;
       } else if (ATL && lb == kNoB) {
         // no g-passing B: the carried partials the g-failing rows so far spared
@@ -1514,7 +1587,7 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
         if (drop == 0 && cap <= S) {
           nn = n;   // unchanged, in place
         } else {
-          if (n > 2) CF_COUNT(3, 1);
+          if (n > 2) CFW_COUNT(3, 1);
           for (int j = drop; j < n; ++j) {
             const uint64_t ts = slot_word(j, 0);
             const uint64_t x0 = c1 ? slot_word(j, 2) : 0ull, x1 = c2 ? slot_word(j, 3) : 0ull;
@@ -1524,7 +1597,7 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
       }
       // partials created after the last B (a record that is both B and A
       // starts a partial after completing others)
-      for (uint32_t q = (lb == kNoB ? r0 : (uint32_t)lb); q < r1 && !(a.ablate & 2); ++q) {
+      for (uint32_t q = (lb == kNoB ? r0 : (uint32_t)lb); q < r1 && !(ablate & 2); ++q) {
         if (!((L.skr[q] >> 12) & ROLE_A)) continue;
         if (TOL && !(L.skr[q] & kSkrAlive)) continue;   // expired before the run ended
         const int64_t ats = ts_base + (int64_t)L.sts[q];
@@ -1539,25 +1612,28 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
                  cp1 < 0 ? (uint64_t)ats : (cp1 == 0 ? a0 : a1));
       }
       dirty |= nn != n;
-      if (nn > S) ovo = noff | kOvoWr;
+      if (nn > S) {
+        if (noff == kNoOff) nn = S;   // (only after the pool ran out: no run to point at)
+        else cf_ovf_commit(a.kext + kidx, nn, noff);
+      }
       n = nn;
     }
 #ifndef CF_WAVESTAMP
-    CF_STAMP(wi * 8 + 6);
+    CFW_STAMP(wi * 8 + 6);
 #else
-    CF_WSTAMP(1 + (int)(threadIdx.x >> 6));
+    CFW_WSTAMP(1 + (int)(threadIdx.x >> 6));
 #endif
 
     // ---- emit record matches: lane per output row from omap (consecutive
     // lanes write consecutive rows, every lane busy), or lane per sorted
     // position when the window has more record matches than omap lists
     const uint32_t nrec = L.nrec;
-    const bool compact = nrec <= (uint32_t)kCfOmap && !(a.ablate & 8);   // ablate 8: per position
+    const bool compact = nrec <= (uint32_t)kCfOmap && !(ablate & 8);   // ablate 8: per position
     const uint32_t nemit = compact ? nrec : (uint32_t)(PER * NT);
 #pragma unroll 1
     for (uint32_t j = tid; j < nemit; j += NT) {
       const uint32_t q = compact ? (uint32_t)omap[j] : j;
-      if (q >= nw || (a.ablate & 4)) continue;   // ablate 4 (diagnostics): no record-match stores
+      if (q >= nw || (ablate & 4)) continue;   // ablate 4 (diagnostics): no record-match stores
       const uint32_t kr = L.skr[q];
       const uint16_t nb = L.nextb[q];
       if (!((kr >> 12) & ROLE_A) || nb == kNoB) continue;
@@ -1580,9 +1656,9 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
               seq_base + (int64_t)L.sseq[nb]);
     }
 #ifndef CF_WAVESTAMP
-    CF_STAMP(wi * 8 + 7);
+    CFW_STAMP(wi * 8 + 7);
 #else
-    CF_WSTAMP(9 + (int)(threadIdx.x >> 6));
+    CFW_WSTAMP(9 + (int)(threadIdx.x >> 6));
 #endif
     if (over) {
       piece += nw;
@@ -1600,7 +1676,7 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
     // the previous window used, read by nobody since: zeroed without a
     // second barrier (its counts are added after the next window's first)
     lds_barrier();
-    CF_STAMP(8);   // window 1 only: after the window-end barrier
+    CFW_STAMP(8);   // window 1 only: after the window-end barrier
     kbuf ^= 1;
     for (int k = tid; k <= kpb; k += NT) L.kstart[kbuf][k] = 0;
   }
@@ -1608,7 +1684,7 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
   // in an in-order chunk every remaining partial precedes that row unless
   // its ts is above the row's (then it is not expired), so the latest row
   // alone decides.  Compacted in place, slot order kept.
-  if (ATL && klane && n > 0 && mpb != 0u && W >= 0 && !(a.ablate & 32)) {
+  if (ATL && klane && n > 0 && mpb != 0u && W >= 0 && !(ablate & 32)) {
     cn = 0;   // the last window's pcache copy may be stale: slots >= 2 from HBM
     int nn = 0;
     for (int j = 0; j < n; ++j) {
@@ -1629,7 +1705,7 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
           if (c1) sl_st(nn, 2, x0);
           if (c2) sl_st(nn, 3, x1);
         } else {   // within the key's own overflow run (nn < j)
-          uint64_t* o = (uint64_t*)ovp() + (int64_t)(nn - S) * sw;
+          uint64_t* o = cf_ovf_ptr(a.pool_rd, a.pool_wr, a.kext + kidx, sw, (int64_t)(nn - S) * sw);
           o[0] = ts;
           if (c1) o[2] = x0;
           if (c2) o[3] = x1;
@@ -1663,23 +1739,12 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
   }
   // ---- an overflow run still in the read pool moves to the write pool
   // (the read pool is the next launch's write pool)
-  if (klane && n > S && !(ovo & kOvoWr)) {
-    const unsigned long long cnt = (unsigned long long)(n - S);
-    const unsigned long long off = atomicAdd(a.pool_cursor, cnt);
-    if (off + cnt > a.pool_cap) {
-      set_err(a.err, ERR_POOL);
-    } else {
-      uint64_t* o = a.pool_wr + off * (uint64_t)sw;
-      const uint64_t* src = ovp();
-      for (int64_t i = 0; i < (int64_t)cnt * sw; ++i) o[i] = src[i];
-      ovo = (uint32_t)off | kOvoWr;
-      dirty = true;
-    }
-  }
+  // (and kext takes its final form: count | offset in that pool)
+  if (klane && n > S)
+    dirty |= cf_ovf_finish(a.pool_rd, a.pool_wr, a.pool_cursor, a.pool_cap, a.err, a.kext + kidx, n, S, sw);
   // ---- the key's header and register-resident slots 0 / 1, once
   if (klane && dirty) {
     const uint32_t h1 = (a.khdr[kidx] & ~(0xffu | kHdrOvf)) | (n > S ? ((uint32_t)S | kHdrOvf) : (uint32_t)n);
-    if (n > S) a.kext[kidx] = (uint64_t)(uint32_t)n | ((uint64_t)(ovo & ~kOvoWr) << 32);
     if (n > 0) {
       sl_st(0, 0, t0r);
       if (c1) sl_st(0, 2, a0c0);
@@ -1694,9 +1759,19 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
   }
 }
 
+// LEAN: the common-case instance (launch_cf_walk: no diagnostics, no in_seq
+// lookup, no diversion); the other keeps every feature behind its run-time
+// argument.
+template <int NW, bool KR, int NC, bool TOL = false, bool ATL = false, bool LEAN = false>
+__global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   // 2 workgroups per CU
+  __shared__ CfWalkLds<NW> L;
+  cf_walk_body<NW, KR, NC, TOL, ATL, LEAN ? 0 : kWfAll>(a, L);
+}
+
 // Kernel instances are spread over translation units (CF_UNIT, Makefile)
 // so they compile in parallel: unit 1 the route and the dispatchers, units
-// 2-7 one walk mode x key-value build each, unit 8 the order-tolerant and
+// 2-7 one walk mode x key-value build each (every feature), units 15-20 the
+// same six as common-case instances, unit 8 the order-tolerant and
 // received-record partitions, units 9-14 the event-time / adaptive
 // partitions per carried-word count.
 void cf_part_tol(const CfPartArgs& a, int64_t ntiles, hipStream_t s);
@@ -1706,6 +1781,12 @@ void cf_walk_tol0(const CfWalkArgs& a, int nbuckets, hipStream_t s);
 void cf_walk_tol1(const CfWalkArgs& a, int nbuckets, hipStream_t s);
 void cf_walk_atl0(const CfWalkArgs& a, int nbuckets, hipStream_t s);
 void cf_walk_atl1(const CfWalkArgs& a, int nbuckets, hipStream_t s);
+void cf_walk_et0c(const CfWalkArgs& a, int nbuckets, hipStream_t s);
+void cf_walk_et1c(const CfWalkArgs& a, int nbuckets, hipStream_t s);
+void cf_walk_tol0c(const CfWalkArgs& a, int nbuckets, hipStream_t s);
+void cf_walk_tol1c(const CfWalkArgs& a, int nbuckets, hipStream_t s);
+void cf_walk_atl0c(const CfWalkArgs& a, int nbuckets, hipStream_t s);
+void cf_walk_atl1c(const CfWalkArgs& a, int nbuckets, hipStream_t s);
 
 #if !defined(CF_UNIT) || CF_UNIT == 8
 void cf_part_tol(const CfPartArgs& a, int64_t ntiles, hipStream_t s) {
@@ -1797,52 +1878,81 @@ void launch_cf_partition(const CfPartArgs& a, int64_t ntiles, hipStream_t s) {
 }
 #endif  // CF_UNIT 1
 
-template <int NW, bool KR, bool TOL = false, bool ATL = false>
+template <int NW, bool KR, bool TOL, bool ATL, bool LEAN>
 static void launch_cf_walk_nc(const CfWalkArgs& a, int nbuckets, hipStream_t s) {
   const dim3 g((unsigned)nbuckets), b(kCfWalkThreads);
   switch (a.pat.slot_words - 2) {
-    case 0: hipLaunchKernelGGL((k_cfwalk<NW, KR, 0, TOL, ATL>), g, b, 0, s, a); break;
-    case 1: hipLaunchKernelGGL((k_cfwalk<NW, KR, 1, TOL, ATL>), g, b, 0, s, a); break;
-    default: hipLaunchKernelGGL((k_cfwalk<NW, KR, 2, TOL, ATL>), g, b, 0, s, a); break;
+    case 0: hipLaunchKernelGGL((k_cfwalk<NW, KR, 0, TOL, ATL, LEAN>), g, b, 0, s, a); break;
+    case 1: hipLaunchKernelGGL((k_cfwalk<NW, KR, 1, TOL, ATL, LEAN>), g, b, 0, s, a); break;
+    default: hipLaunchKernelGGL((k_cfwalk<NW, KR, 2, TOL, ATL, LEAN>), g, b, 0, s, a); break;
   }
 }
 
-template <bool KR, bool TOL, bool ATL>
+template <bool KR, bool TOL, bool ATL, bool LEAN>
 static void cf_walk_mode(const CfWalkArgs& a, int nbuckets, hipStream_t s) {
   switch (a.cf.nw) {
-    case 0: launch_cf_walk_nc<0, KR, TOL, ATL>(a, nbuckets, s); break;
-    case 1: launch_cf_walk_nc<1, KR, TOL, ATL>(a, nbuckets, s); break;
-    default: launch_cf_walk_nc<2, KR, TOL, ATL>(a, nbuckets, s); break;
+    case 0: launch_cf_walk_nc<0, KR, TOL, ATL, LEAN>(a, nbuckets, s); break;
+    case 1: launch_cf_walk_nc<1, KR, TOL, ATL, LEAN>(a, nbuckets, s); break;
+    default: launch_cf_walk_nc<2, KR, TOL, ATL, LEAN>(a, nbuckets, s); break;
   }
 }
+// cf_walk_<mode><KR>: every feature; cf_walk_<mode><KR>c: the common case
+#define CF_WALK_UNIT(name, KR, TOL, ATL, LEAN) \
+  void name(const CfWalkArgs& a, int nb, hipStream_t s) { cf_walk_mode<KR, TOL, ATL, LEAN>(a, nb, s); }
 #if !defined(CF_UNIT) || CF_UNIT == 2
-void cf_walk_et0(const CfWalkArgs& a, int nb, hipStream_t s) { cf_walk_mode<false, false, false>(a, nb, s); }
+CF_WALK_UNIT(cf_walk_et0, false, false, false, false)
 #endif
 #if !defined(CF_UNIT) || CF_UNIT == 3
-void cf_walk_et1(const CfWalkArgs& a, int nb, hipStream_t s) { cf_walk_mode<true, false, false>(a, nb, s); }
+CF_WALK_UNIT(cf_walk_et1, true, false, false, false)
 #endif
 #if !defined(CF_UNIT) || CF_UNIT == 4
-void cf_walk_tol0(const CfWalkArgs& a, int nb, hipStream_t s) { cf_walk_mode<false, true, false>(a, nb, s); }
+CF_WALK_UNIT(cf_walk_tol0, false, true, false, false)
 #endif
 #if !defined(CF_UNIT) || CF_UNIT == 5
-void cf_walk_tol1(const CfWalkArgs& a, int nb, hipStream_t s) { cf_walk_mode<true, true, false>(a, nb, s); }
+CF_WALK_UNIT(cf_walk_tol1, true, true, false, false)
 #endif
 #if !defined(CF_UNIT) || CF_UNIT == 6
-void cf_walk_atl0(const CfWalkArgs& a, int nb, hipStream_t s) { cf_walk_mode<false, false, true>(a, nb, s); }
+CF_WALK_UNIT(cf_walk_atl0, false, false, true, false)
 #endif
 #if !defined(CF_UNIT) || CF_UNIT == 7
-void cf_walk_atl1(const CfWalkArgs& a, int nb, hipStream_t s) { cf_walk_mode<true, false, true>(a, nb, s); }
+CF_WALK_UNIT(cf_walk_atl1, true, false, true, false)
 #endif
+#if !defined(CF_UNIT) || CF_UNIT == 15
+CF_WALK_UNIT(cf_walk_et0c, false, false, false, true)
+#endif
+#if !defined(CF_UNIT) || CF_UNIT == 16
+CF_WALK_UNIT(cf_walk_et1c, true, false, false, true)
+#endif
+#if !defined(CF_UNIT) || CF_UNIT == 17
+CF_WALK_UNIT(cf_walk_tol0c, false, true, false, true)
+#endif
+#if !defined(CF_UNIT) || CF_UNIT == 18
+CF_WALK_UNIT(cf_walk_tol1c, true, true, false, true)
+#endif
+#if !defined(CF_UNIT) || CF_UNIT == 19
+CF_WALK_UNIT(cf_walk_atl0c, false, false, true, true)
+#endif
+#if !defined(CF_UNIT) || CF_UNIT == 20
+CF_WALK_UNIT(cf_walk_atl1c, true, false, true, true)
+#endif
+#undef CF_WALK_UNIT
 
 #if !defined(CF_UNIT) || CF_UNIT == 1
 void launch_cf_walk(const CfWalkArgs& a, int nbuckets, hipStream_t s) {
   const bool kr = a.key_rev != nullptr;
+  // what the host knows picks the instance: the common case has no
+  // diagnostics, no arrival-number lookup for received records and no
+  // diverted keys
+  const bool lean = !a.stamps && !a.ablate && !(a.in_seq && a.out.write_seq) && !a.hot_id;
   if (a.atol) {   // adaptive chunk (ts_order 0, in order)
-    kr ? cf_walk_atl1(a, nbuckets, s) : cf_walk_atl0(a, nbuckets, s);
+    if (lean) kr ? cf_walk_atl1c(a, nbuckets, s) : cf_walk_atl0c(a, nbuckets, s);
+    else kr ? cf_walk_atl1(a, nbuckets, s) : cf_walk_atl0(a, nbuckets, s);
   } else if (a.pat.tolerant) {   // order-tolerant records (ts_order 0), dense or sparse keys
-    kr ? cf_walk_tol1(a, nbuckets, s) : cf_walk_tol0(a, nbuckets, s);
+    if (lean) kr ? cf_walk_tol1c(a, nbuckets, s) : cf_walk_tol0c(a, nbuckets, s);
+    else kr ? cf_walk_tol1(a, nbuckets, s) : cf_walk_tol0(a, nbuckets, s);
   } else {
-    kr ? cf_walk_et1(a, nbuckets, s) : cf_walk_et0(a, nbuckets, s);
+    if (lean) kr ? cf_walk_et1c(a, nbuckets, s) : cf_walk_et0c(a, nbuckets, s);
+    else kr ? cf_walk_et1(a, nbuckets, s) : cf_walk_et0(a, nbuckets, s);
   }
 }
 #endif  // CF_UNIT 1

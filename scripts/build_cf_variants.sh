@@ -11,7 +11,8 @@ for spec in "$@"; do
   objs=""
   for o in build/frontend.o build/engine.o build/operator.o build/kernels.o build/reorder.o build/keymap.o \
            build/hot.o build/mq_kernels.o build/filter.o build/cf_u1.o build/cf_u2.o build/cf_u3.o build/cf_u4.o \
-           build/cf_u5.o build/cf_u6.o build/cf_u7.o build/cf_u8.o; do objs="$objs $o"; done
+           build/cf_u5.o build/cf_u6.o build/cf_u7.o build/cf_u8.o build/cf_u15.o build/cf_u16.o build/cf_u17.o \
+           build/cf_u18.o build/cf_u19.o build/cf_u20.o; do objs="$objs $o"; done
   for u in 9 10 11 12 13 14; do
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC $flags -DCF_UNIT=$u --offload-arch=gfx950 -c csrc/cf_kernels.hip -o exp/cf_u$u.$name.o &
     objs="$objs exp/cf_u$u.$name.o"
