@@ -2323,6 +2323,11 @@ int error_status(cep_app* a, unsigned int e) {
   if (e & ERR_ORDER)   // root cause first: out-of-order input also defeats `within` pruning
     return fail(a, CEP_E_ARG, "events not in event-time order: `within` requires non-decreasing timestamps "
                               "(so does group by with #window.time outside a partition)");
+  // before the capacity flags: a time that did not fit its 32-bit field was
+  // stored truncated, so partials and window rows stop expiring and the lists
+  // overflow as a consequence
+  if (e & ERR_TS_SPAN)
+    return fail(a, CEP_E_ARG, "timestamps of one chunk lie more than 2^31 ms apart (lower chunk_events)");
   if (e & ERR_PENDING)
     return fail(a, CEP_E_CAPACITY, "per-key pending partial capacity exceeded (raise pending_slots)");
   if (e & ERR_POOL)
@@ -2339,8 +2344,6 @@ int error_status(cep_app* a, unsigned int e) {
   if (e & ERR_DERIVE)
     return fail(a, CEP_E_UNSUPPORTED, "a row passed the filters of two derived streams that one query reads "
                                       "(it would be two events of that query; make the producers' filters disjoint)");
-  if (e & ERR_TS_SPAN)
-    return fail(a, CEP_E_ARG, "timestamps of one chunk lie more than 2^31 ms apart (lower chunk_events)");
   if (e & ERR_OUT_CAP) return fail(a, CEP_E_DEVICE, "output capacity exceeded");
   return fail(a, CEP_E_DEVICE, "device error flags " + std::to_string(e));
 }

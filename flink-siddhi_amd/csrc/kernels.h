@@ -67,7 +67,15 @@ enum : uint32_t {
   ERR_WINDOW = 16u,          // bucket window logic error
   ERR_POOL = 32u,            // pending overflow pool exhausted
   ERR_KEYMAP = 64u,          // more distinct partition values than key_capacity (sparse keys)
-  ERR_TS_SPAN = 128u,        // a chunk's ts lie more than 2^31 ms either side of its first row
+  // A row's ts does not fit the 32-bit offset from its chunk's first row.  Every
+  // path accepts rows up to 2^31 - 1 ms after it.  Past that: the closed form
+  // in event time and its adaptive build store the offset unsigned (up to
+  // 2^32 - 1 ms after; a row before the first row is a descent: ERR_ORDER /
+  // the order-tolerant build takes the chunk); the order-tolerant closed form
+  // and its hot-key scans bias it by 2^31 (2^31 ms before .. 2^31 - 1 ms
+  // after); k_partition (general walks, windows, received records: +-(2^31 - 1)
+  // ms) and k_mqpart (-2^31 .. 2^31 - 1 ms) store it signed.
+  ERR_TS_SPAN = 128u,
   ERR_SHUFFLE_CAP = 256u,    // padded key shuffle: an owner segment held more than seg_cap records
   ERR_DERIVE = 512u,         // query chaining: a row passed the filters of two derived streams one query reads
 };

@@ -609,8 +609,8 @@ __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs a) {
         if (a.from_records) {
           const uint64_t* in = a.in_recs + r * a.in_rec_words;
           const int64_t dseq = (int64_t)in[1] - seq_base, dts = (int64_t)in[2] - ts_base;
-          if (dseq < 0 || dseq > 0xffffffffll || dts > 0x7fffffffll || dts < -0x7fffffffll)
-            set_err(a.err, ERR_ORDER);
+          if (dseq < 0 || dseq > 0xffffffffll) set_err(a.err, ERR_ORDER);
+          if (dts > 0x7fffffffll || dts < -0x7fffffffll) set_err(a.err, ERR_TS_SPAN);
           put(0, (in[0] & ~0xffffffffull) | (uint64_t)(uint32_t)key[e]);
           put(1, (uint64_t)(uint32_t)((int64_t)in[1] - seq_base) |
                    ((uint64_t)(uint32_t)(int32_t)((int64_t)in[2] - ts_base) << 32));
@@ -627,7 +627,7 @@ __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs a) {
         s = a.rows.stream ? (int)a.rows.stream[r] : a.rows.input;
         dts = a.rows.ts[r] - ts_base;
       }
-      if (dts > 0x7fffffffll || dts < -0x7fffffffll) set_err(a.err, ERR_ORDER);
+      if (dts > 0x7fffffffll || dts < -0x7fffffffll) set_err(a.err, ERR_TS_SPAN);
       put(0, (uint64_t)(uint32_t)key[e] | ((uint64_t)role << 32) | ((uint64_t)(uint32_t)s << 40));
       int64_t dseq = r - a.rows.row0;
       if (a.rows.seq) {   // shuffled rows: global arrival numbers, increasing

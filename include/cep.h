@@ -153,9 +153,19 @@ typedef struct cep_options {
                               when SURVEY App. A.3 drops it (|ts(event) - ts(s1)| > W, on
                               events of that stream), so the state and every match equal the
                               oracle's for any order.  `every A -> B` patterns take the
-                              closed form's order-tolerant build (hot keys included; a
-                              chunk's ts must lie within +-2^31 ms of its first row's, else
-                              the flush fails with CEP_E_ARG), other shapes the N-state walk.
+                              closed form's order-tolerant build (hot keys included), other
+                              shapes the N-state walk.
+                              Either way every pattern, window and multi-query kernel
+                              stores a row's ts as a 32-bit offset from the first row of its
+                              chunk (chunk_events rows of one batch): rows up to 2^31 - 1 ms
+                              after that row are exact on every path, and with ts_order 0
+                              rows up to 2^31 - 1 ms before it.  A wider chunk fails the
+                              flush with CEP_E_ARG ("timestamps of one chunk lie more than
+                              2^31 ms apart"; the closed form in event time and its adaptive
+                              build still take rows up to 2^32 - 1 ms after the first); lower
+                              chunk_events or split the batch at the gap.  Gaps between
+                              chunks, `within` and the absolute value of ts are not limited:
+                              per-key state holds 64-bit times.
                               1: the caller guarantees non-decreasing ts (event-time order,
                               e.g. a watermark drain with late_policy 0): the event-time fast
                               paths (closed form, predicate push-down of B's, pruning at A
