@@ -477,7 +477,15 @@ bool mq_candidate(const cep_app* a, const Query& q, MqNeeds* nd) {
   }
   for (auto& cp : q.ncaps) {
     if (cp.index != 0 && cp.index != -1) return false;
-    carry(q.rec_cols_a[cp.word]);
+    // the group units clear a new partial's captures to 0, which is the null
+    // of every type but STRING (dictionary id -1, cep.h): a STRING capture of
+    // a state a match may skip stays on the stand-alone walk (cap_null)
+    const auto& cs = q.nstates[cp.state];
+    const int ccol = q.rec_cols_a[cp.word];
+    if (cs.min_count == 0 && ccol >= 0 && ccol < (int)app.inputs[cs.stream].attrs.size() &&
+        app.inputs[cs.stream].attrs[ccol].type == T_STRING)
+      return false;
+    carry(ccol);
   }
   for (auto& it : q.select)
     if (!(it.src == SRC_KEY || (it.src >= SRC_CAP && it.src < SRC_CAP + (int)q.ncaps.size()))) return false;

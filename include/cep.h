@@ -201,7 +201,16 @@ typedef struct {
   int32_t on_device;          /* 1: ts/stream/cols are device pointers */
 } cep_batch;
 
-/* Output rows, columnar, in emission order (see cep_options.ordered_output). */
+/* Output rows, columnar, in emission order (see cep_options.ordered_output).
+ *
+ * Null: a select item that reads a capture of a pattern / sequence state that
+ * never matched (an optional state `?`, `*`, `<0:n>` the match skipped, or
+ * sK[n] of a state that collected fewer than n + 1 events) is null in Siddhi.
+ * Columns carry no validity bits; in an output row such an item is
+ *   - 0 for INT, LONG, FLOAT, DOUBLE (all bits zero) and false for BOOL,
+ *   - dictionary id -1 for STRING (no string has it: cep_dict_lookup(-1) is
+ *     NULL),
+ * on every path (stand-alone walk and multi-query groups alike). */
 typedef struct {
   const char* stream_id;
   int64_t n;
