@@ -12,6 +12,9 @@
 //             term lists, rows no state can use dropped, LDS histogram over
 //             the P key buckets, LDS scan, 16-byte records staged in LDS and
 //             stored as one contiguous run per tile (coalesced).
+//   k_cfpart2 the same partition for the event-time build on local rows
+//             without diversion (config 3), two 512-lane workgroups per CU:
+//             a tile in two halves, kept rows parked in LDS (see there).
 //   k_cfwalk  one 1024-lane workgroup per key bucket (<= 512 keys): gathers
 //             the bucket's segment of every tile (tile order = arrival
 //             order), counting sort by key in LDS + arrival sort per key run,
@@ -441,6 +444,283 @@ __global__ __launch_bounds__(kCfPartThreads, CF_PART_MINW) void k_cfpart(CfPartA
     }
   }
   CF_STAMP(5);
+}
+
+// ============================================================= k_cfpart2 ==
+// The event-time partition of local rows without diversion (config 3's), as
+// two 512-lane workgroups per CU: while one works in LDS the other's loads
+// keep the CU's memory pipe busy.  Same arguments and the same output as
+// k_cfpart<NW, false, NP> (records bucket-major per tile, order inside a
+// segment free; tile_off; chunk_base; pool cursor; order check; ERR_*).
+//
+// What makes 128 VGPRs enough: no row lives in registers past its half.  A
+// lane loads its 16 rows as two halves of 8 (half h, wave w, row e: tile row
+// h * 4096 + w * 512 + 64 e + lane; a plan that reads four columns, whose
+// predicates then have no registers left beside 8 rows of them, takes four
+// quarters of 4 rows per lane) and a kept row (~1/3 at config 3) goes
+// to an LDS pending area at once, in arrival-free compact order: {w0,
+// carried words} and bucket << 13 | rank in bucket (the LDS histogram's
+// atomicAdd).  After the scan of the histogram a u16 table maps each output
+// slot to its pending record, and the tile is copied out in bucket order
+// with 16-byte coalesced stores.
+//
+// A tile that keeps more rows than the pending area holds (pending writes
+// are bounded; the histogram still counts every kept row, so the overflow is
+// known, uniformly, after the scan) is redone: its rows are loaded and
+// evaluated again and each kept row is stored straight to its HBM slot,
+// taken from a consuming cursor per bucket (the scanned histogram).
+constexpr int kCf2Threads = 512;
+// rows per lane and load group: a tile is kCfTile / (kCf2Threads * E) such parts
+template <int NP>
+constexpr int cf2_items() { return NP > 3 ? kCfItems / 2 : kCfItems; }
+constexpr int kCf2LdsBytes = 80 * 1024;            // per workgroup, everything: two per CU
+// pending records: what the largest histogram (kCfMaxBuckets + 1 words, dynamic
+// LDS) and the scan's scratch leave, at 8 RW + 4 (bucket | rank) + 2 (slot
+// table) bytes each; 2968 at RW = 2 (a config-3 tile keeps 2633 +- 42)
+template <int RW>
+constexpr int cf2_pending() {
+  return ((kCf2LdsBytes - (kCfMaxBuckets + 4) * 4 - 64) / (8 * RW + 6)) & ~7;
+}
+
+// The kernel's arguments (CfPartArgs is k_cfpart2's only parameter, so it
+// sits at the start of the kernel-argument segment), behind a pointer the
+// compiler cannot see through.  Each half of a tile reads what it needs
+// through its own: with the plain parameter every uniform value of a half
+// (column bases, term descriptors, plan scalars and all that is computed from
+// them) is shared with, or hoisted above, the other half and stays live
+// across both: 800 SGPRs and 200 VGPRs spilled.  Read afresh, nothing lives
+// from one half to the next and the kernel has no scratch.
+__device__ __forceinline__ const CfPartArgs& cf2_args() {
+  auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(kp));
+  return *(const CfPartArgs*)kp;
+}
+
+// One half (part h) of a tile: loads, order check, f / g, then per kept row
+// its bucket rank and (DIRECT: redo of an overflowing tile) its HBM slot, else
+// its pending record.  Every lane of the workgroup calls it (wave scan inside).
+template <int NW, int NP, bool DIRECT>
+__device__ __forceinline__ void cf2_half(int64_t tile, int h, bool full, int64_t ts_base, uint32_t* hist,
+                                         uint64_t* pend, uint32_t* pbr, uint32_t* s_cnt, uint64_t* trecs) {
+  constexpr int E = cf2_items<NP>(), RW = 1 + NW;
+  constexpr uint32_t CAP = (uint32_t)cf2_pending<RW>();
+  const CfPartArgs& a = cf2_args();
+  const PatternArgs& p = a.pat;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lg = p.buckets_log2;
+  const int P = 1 << lg;
+  const uint32_t trow = (uint32_t)(h * kCf2Threads * E + wave * 64 * E + lane);   // tile row of e = 0
+  const int64_t r0 = tile * kCfTile + trow;      // chunk-relative
+  const int64_t row0 = a.rows.row0 + r0;         // batch row
+  uint32_t valid = 0;
+#pragma unroll
+  for (int e = 0; e < E; ++e) valid |= (r0 + 64 * e < a.rows.n ? 1u : 0u) << e;
+  // what a row keeps past the loads: its role, bucket and key in bucket (bk
+  // = bucket | key in bucket << 12), ts - chunk base and carried words
+  uint32_t role_a = 0, role_b = 0, keep = 0;
+  uint32_t bk[E], dts[E];
+  uint64_t fc0[E], fc1[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    bk[e] = dts[e] = 0;
+    fc0[e] = fc1[e] = 0;
+  }
+  if (valid) {
+    uint64_t tsv[E];
+    uint64_t pv[NP][E];
+    uint32_t sb[E];
+    int64_t before_full = 0;
+    if (full) cf_load_cols_full<E, NP>(a.rows, a.pref, a.ts_slot, row0, tsv, sb, pv, &before_full);
+    else cf_load_cols<E, NP>(a.rows, a.pref, a.ts_slot, row0, valid, tsv, sb, pv);
+    uint32_t is_a = 0, is_b = 0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      if ((valid >> e) & 1u) {
+        is_a |= ((int)sb[e] == p.a_stream ? 1u : 0u) << e;
+        is_b |= ((int)sb[e] == p.b_stream ? 1u : 0u) << e;
+      }
+    }
+    if (p.within >= 0) {
+      // event-time order check, as k_cfpart: row r - 1 is held by the previous
+      // lane (same e), lane 63 (e - 1), or loaded (per wave and half)
+      int64_t before;
+      if (full) before = row0 > 0 ? before_full : batch_prev_ts(a.rows);
+      else before = row0 > 0 ? a.rows.ts[row0 - 1] : batch_prev_ts(a.rows);
+      bool bad = false;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const uint64_t up = __shfl_up(tsv[e], 1, 64);
+        const uint64_t last = e > 0 ? __shfl(tsv[e > 0 ? e - 1 : 0], 63, 64) : 0ull;
+        const int64_t prev = lane > 0 ? (int64_t)up : (e > 0 ? (int64_t)last : before);
+        if ((valid >> e) & 1u) bad |= (int64_t)tsv[e] < prev;
+      }
+      if (bad) report_descent(a.rows, a.err);
+    }
+    // ts - chunk base now (32 bits, out-of-range rows noted), so the 64-bit
+    // ts are not live through the predicates
+    uint32_t neg = 0, big = 0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int64_t d = (int64_t)tsv[e] - ts_base;
+      neg |= (d < 0 ? 1u : 0u) << e;
+      big |= (d > 0xffffffffll ? 1u : 0u) << e;
+      dts[e] = (uint32_t)d;
+    }
+    const uint32_t all = (1u << E) - 1u;
+    if (is_a) role_a = is_a & (p.f_prog < 0 ? all : eval_terms_regs<E, NP>(p.f_terms, a.pref.f_slot, a.rows.cols, pv));
+    if (is_b) role_b = is_b & (p.g_raw_prog < 0 ? all : eval_terms_regs<E, NP>(p.g_terms, a.pref.g_slot, a.rows.cols, pv));
+    // kept rows: a role and a key in range (the host puts the key column in slot 0)
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      if (!(((role_a | role_b) >> e) & 1u)) continue;
+      const int64_t key = a.pref.key_slot >= 0 ? (int64_t)pv[0][e] : 0;
+      const int64_t kfield = shard_key(key, p.key_stride, p.key_offset);
+      if (kfield < 0 || kfield >= p.key_capacity) {
+        set_err(a.err, ERR_KEY_RANGE);
+        continue;
+      }
+      keep |= 1u << e;
+      bk[e] = (uint32_t)(kfield & (P - 1)) | ((uint32_t)(kfield >> lg) << 12);
+      if ((neg >> e) & 1u) report_descent(a.rows, a.err);
+      else if ((big >> e) & 1u) set_err(a.err, ERR_TS_SPAN);
+    }
+    if (NW > 0) pick_carried<E, NP>(pv, a.cf.a_slot[0], a.cf.b_slot[0], role_a, fc0);
+    if (NW > 1) pick_carried<E, NP>(pv, a.cf.a_slot[1], a.cf.b_slot[1], role_a, fc1);
+  }
+  // compact pending slots: a lane's kept rows take consecutive ones, a wave
+  // takes its range with one LDS atomic
+  uint32_t slot = 0;
+  if (!DIRECT) {
+    const uint32_t nk = (uint32_t)__popc(keep);
+    const uint32_t incl = wave_incl_scan(nk);
+    uint32_t base = 0;
+    if (lane == 63) base = atomicAdd(s_cnt, incl);
+    base = (uint32_t)__shfl((int)base, 63, 64);
+    slot = base + incl - nk;
+  }
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    if (!((keep >> e) & 1u)) continue;
+    const uint32_t role = ((role_a >> e) & 1u) * ROLE_A | ((role_b >> e) & 1u) * ROLE_B;
+    const uint32_t bucket = bk[e] & 0xfffu;
+    const uint64_t w0 = (uint64_t)dts[e] | ((uint64_t)(trow + 64 * e) << 32) | ((uint64_t)role << 45) |
+                        ((uint64_t)(bk[e] >> 12) << 48);
+    const uint32_t rank = atomicAdd(&hist[bucket], 1u);   // DIRECT: the tile slot (consuming cursor)
+    if (DIRECT) {
+      uint64_t* g = trecs + (int64_t)rank * RW;
+      g[0] = w0;
+      if (NW > 0) g[1] = fc0[e];
+      if (NW > 1) g[2] = fc1[e];
+    } else {
+      if (slot < CAP) {   // bounded: a tile that keeps more is redone (DIRECT)
+        pend[slot * RW] = w0;
+        if (NW > 0) pend[slot * RW + 1] = fc0[e];
+        if (NW > 1) pend[slot * RW + 2] = fc1[e];
+        pbr[slot] = (bucket << 13) | rank;
+      }
+      ++slot;
+    }
+  }
+}
+
+template <int NW, int NP>
+__global__ __launch_bounds__(kCf2Threads, 4) void k_cfpart2(CfPartArgs a) {
+  constexpr int NT = kCf2Threads, RW = 1 + NW;
+  constexpr int NPART = kCfTile / (NT * cf2_items<NP>());   // 2 halves (4 quarters at NP = 4)
+  static_assert(NPART * NT * cf2_items<NP>() == kCfTile && kCfItems == 8, "a tile is whole parts");
+  constexpr int CAP = cf2_pending<RW>();
+  __shared__ uint32_t scratch[NT / 64 + 1];
+  __shared__ uint32_t s_cnt;                                          // pending slots handed out
+  __shared__ __attribute__((aligned(16))) uint64_t pend[CAP * RW];    // kept rows' records, compact
+  __shared__ uint32_t pbr[CAP];                                       // bucket << 13 | rank of each
+  __shared__ uint16_t sidx[CAP];                                      // output slot -> pending record
+  extern __shared__ __attribute__((aligned(16))) uint32_t hist[];     // P + 1 (dynamic)
+  const int tid = threadIdx.x;
+  const int64_t tile = xcd_tile(blockIdx.x, a.ntiles);
+  // staggered first round (see k_cfpart): here it is two workgroups per CU
+  if (a.stagger > 0 && blockIdx.x < 2 * kCfStaggerBlocks) {
+    const uint64_t t0 = __builtin_amdgcn_s_memtime();
+    const uint64_t d = (uint64_t)((blockIdx.x >> 3) & 63u) * (uint64_t)a.stagger / 2;
+    while (__builtin_amdgcn_s_memtime() - t0 < d) __builtin_amdgcn_s_sleep(8);
+  }
+  const int P = 1 << a.pat.buckets_log2;
+  CF_STAMP(0);
+  for (int i = tid; i <= P; i += NT) hist[i] = 0;
+  if (tid == 0) s_cnt = 0;
+  const int64_t ts_base = a.rows.ts[a.rows.row0];
+  if (tile == 0 && tid == 0) {
+    if (a.pool_cursor) *a.pool_cursor = 0ull;
+    a.chunk_base[0] = ts_base;
+    a.chunk_base[1] = a.rows.seq0 + a.rows.row0;
+  }
+  const bool full = (tile + 1) * (int64_t)kCfTile <= a.rows.n;   // uniform
+  uint64_t* trecs = a.recs + tile * (int64_t)kCfTile * RW;
+  lds_barrier();   // hist, s_cnt zeroed
+#pragma unroll 1
+  for (int h = 0; h < NPART; ++h) {
+    cf2_half<NW, NP, false>(tile, h, full, ts_base, hist, pend, pbr, &s_cnt, trecs);
+    if (h == 0) CF_STAMP(1);
+  }
+  CF_STAMP(2);
+  lds_barrier();
+  {
+    // exclusive scan of the P bucket counts (P <= 4096: <= 8 per thread)
+    constexpr int MAXPER = kCfMaxBuckets / NT;
+    const int per = (P + NT - 1) / NT;
+    uint32_t c[MAXPER];
+    uint32_t sum = 0;
+#pragma unroll
+    for (int i = 0; i < MAXPER; ++i) {
+      const int idx = tid * per + i;
+      c[i] = (i < per && idx < P) ? hist[idx] : 0u;
+      sum += c[i];
+    }
+    uint32_t total;
+    uint32_t off = bscan<NT>(sum, scratch, &total);
+#pragma unroll
+    for (int i = 0; i < MAXPER; ++i) {
+      const int idx = tid * per + i;
+      if (i < per && idx < P) {
+        hist[idx] = off;
+        off += c[i];
+      }
+    }
+    if (tid == 0) hist[P] = total;
+  }
+  lds_barrier();
+  CF_STAMP(3);
+  const uint32_t total = hist[P];   // kept rows of the tile (= s_cnt)
+  for (int i = tid; i <= P; i += NT) a.tile_off[(int64_t)i * a.ntiles + tile] = (uint16_t)hist[i];
+  if (total <= (uint32_t)CAP) {   // uniform
+    for (uint32_t i = tid; i < total; i += NT) {
+      const uint32_t br = pbr[i];
+      sidx[hist[br >> 13] + (br & 0x1fffu)] = (uint16_t)i;
+    }
+    lds_barrier();
+    CF_STAMP(4);
+    // the tile's records are contiguous in HBM, in bucket order: 16-byte coalesced stores
+    if (RW == 2) {
+      for (uint32_t s = tid; s < total; s += NT)
+        *(uint4*)(trecs + 2 * (int64_t)s) = *(const uint4*)(pend + 2 * (uint32_t)sidx[s]);
+    } else {
+      const uint32_t words = total * RW;
+      for (uint32_t w = 2 * tid; w < words; w += 2 * NT) {
+        const uint64_t x0 = pend[(uint32_t)sidx[w / RW] * RW + w % RW];
+        if (w + 1 < words) {
+          const uint64_t x1 = pend[(uint32_t)sidx[(w + 1) / RW] * RW + (w + 1) % RW];
+          *(uint4*)(trecs + w) = make_uint4((uint32_t)x0, (uint32_t)(x0 >> 32), (uint32_t)x1, (uint32_t)(x1 >> 32));
+        } else {
+          trecs[w] = x0;
+        }
+      }
+    }
+    CF_STAMP(5);
+  } else {
+    lds_barrier();   // tile_off has read the scanned histogram; it becomes the cursors
+#pragma unroll 1
+    for (int h = 0; h < NPART; ++h) cf2_half<NW, NP, true>(tile, h, full, ts_base, hist, pend, pbr, &s_cnt, trecs);
+    CF_STAMP(6);
+  }
 }
 
 #if !defined(CF_UNIT) || CF_UNIT == 1
@@ -1773,7 +2053,8 @@ __global__ __launch_bounds__(kCfWalkThreads, 4) void k_cfwalk(CfWalkArgs a) {   
 // 2-7 one walk mode x key-value build each (every feature), units 15-20 the
 // same six as common-case instances, unit 8 the order-tolerant and
 // received-record partitions, units 9-14 the event-time / adaptive
-// partitions per carried-word count.
+// partitions per carried-word count, units 21-23 the two-workgroup
+// event-time partition (k_cfpart2) per carried-word count.
 void cf_part_tol(const CfPartArgs& a, int64_t ntiles, hipStream_t s);
 void cf_walk_et0(const CfWalkArgs& a, int nbuckets, hipStream_t s);
 void cf_walk_et1(const CfWalkArgs& a, int nbuckets, hipStream_t s);
@@ -1864,10 +2145,51 @@ void cf_part_atl1(const CfPartArgs& a, int64_t n, hipStream_t s) { cf_part_local
 void cf_part_atl2(const CfPartArgs& a, int64_t n, hipStream_t s) { cf_part_local<2, true>(a, n, s); }
 #endif
 
+// the two-workgroup event-time partition (k_cfpart2) of nw carried words
+template <int NW>
+static void cf_part_2wg(const CfPartArgs& a, int64_t ntiles, hipStream_t s) {
+  const int P = 1 << a.pat.buckets_log2;
+  const size_t dyn = ((size_t)(P + 1) * 4 + 15) & ~(size_t)15;
+  const dim3 g((unsigned)ntiles), b(kCf2Threads);
+  const int np = a.pref.n <= 2 ? 2 : a.pref.n;
+  switch (np) {
+    case 2: hipLaunchKernelGGL((k_cfpart2<NW, 2>), g, b, dyn, s, a); break;
+    case 3: hipLaunchKernelGGL((k_cfpart2<NW, 3>), g, b, dyn, s, a); break;
+    default: hipLaunchKernelGGL((k_cfpart2<NW, 4>), g, b, dyn, s, a); break;
+  }
+}
+void cf_part_2wg0(const CfPartArgs&, int64_t, hipStream_t);
+void cf_part_2wg1(const CfPartArgs&, int64_t, hipStream_t);
+void cf_part_2wg2(const CfPartArgs&, int64_t, hipStream_t);
+#if !defined(CF_UNIT) || CF_UNIT == 21
+void cf_part_2wg0(const CfPartArgs& a, int64_t n, hipStream_t s) { cf_part_2wg<0>(a, n, s); }
+#endif
+#if !defined(CF_UNIT) || CF_UNIT == 22
+void cf_part_2wg1(const CfPartArgs& a, int64_t n, hipStream_t s) { cf_part_2wg<1>(a, n, s); }
+#endif
+#if !defined(CF_UNIT) || CF_UNIT == 23
+void cf_part_2wg2(const CfPartArgs& a, int64_t n, hipStream_t s) { cf_part_2wg<2>(a, n, s); }
+#endif
+
 #if !defined(CF_UNIT) || CF_UNIT == 1
+// Which launches take k_cfpart2: the event-time build on local rows with no
+// hot-key diversion, whatever the chunk size (plan and launch properties
+// only); one_wg (CEP_CF_PART=1) keeps k_cfpart there too.
+bool cf_partition_2wg(const CfPartArgs& a) {
+  return !a.in_recs && !a.pat.tolerant && !a.atol && a.nhot == 0 && !a.one_wg;
+}
+
 void launch_cf_partition(const CfPartArgs& a, int64_t ntiles, hipStream_t s) {
   if (a.in_recs || (a.pat.tolerant && !a.atol)) {
     cf_part_tol(a, ntiles, s);
+    return;
+  }
+  if (cf_partition_2wg(a)) {
+    switch (a.cf.nw) {
+      case 0: cf_part_2wg0(a, ntiles, s); break;
+      case 1: cf_part_2wg1(a, ntiles, s); break;
+      default: cf_part_2wg2(a, ntiles, s); break;
+    }
     return;
   }
   switch (a.cf.nw) {

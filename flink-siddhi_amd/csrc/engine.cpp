@@ -273,6 +273,7 @@ struct cep_app {
   DevBuf last_ts_dev;          // last ts of the previous batch (RowsArgs::prev_ts_dev)
   bool force_tolerant = false; // this batch holds late rows (cep_watermark, late_policy 2)
   bool seq_poison = false;     // diagnostics (CEP_SEQ_POISON=1): unread seq columns hold a pattern the flush checks
+  bool cf_one_wg = false;      // CEP_CF_PART=1 (read at creation): k_cfpart where k_cfpart2 would run
   int64_t launches[16] = {0};
   double kernel_ms[16] = {0};
   int64_t kernel_timed[16] = {0};
@@ -991,6 +992,7 @@ int create_runtime(cep_app* a) {
     a->outs.push_back(std::move(o));
     if (const char* e = std::getenv("CEP_SEQ_POISON")) a->seq_poison = std::atoi(e) != 0;
   }
+  if (const char* e = std::getenv("CEP_CF_PART")) a->cf_one_wg = std::atoi(e) == 1;
   {
     const int rc = build_mq_groups(a);
     if (rc) return rc;
@@ -1580,6 +1582,7 @@ int run_pattern_cf(cep_app* a, PatternRT& rt, const Query& q, OutStream& o,
     // (CEP_CF_STAGGER: ticks per step, 0 = off)
     static const int stagger = std::getenv("CEP_CF_STAGGER") ? std::atoi(std::getenv("CEP_CF_STAGGER")) : 1280;
     pa.stagger = ntiles >= 4 * kCfStaggerBlocks ? stagger : 0;
+    pa.one_wg = a->cf_one_wg ? 1 : 0;
     // the pool cursor of this chunk's walk: zeroed by the partition (serial
     // mode), or by a fill on the walk's stream when the partition may run
     // beside the previous walk (CEP_OVERLAP)
@@ -1651,6 +1654,7 @@ int run_pattern_cf(cep_app* a, PatternRT& rt, const Query& q, OutStream& o,
       // (adaptive chunk: the order-tolerant fallback, which returns at once
       // when the chunk was in order)
       LaunchTimer t(a, atol ? CEP_K_OTHER : CEP_K_CF_PARTITION, side);
+      if (cf_partition_2wg(pa)) a->launches[CEP_K_CF_PARTITION_2WG]++;   // (k_cfpart2: counted under both)
       launch_cf_partition(pa, ntiles, side);
     }
     if (overlap) {

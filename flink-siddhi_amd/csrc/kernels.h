@@ -389,6 +389,8 @@ struct CfPartArgs {
   // ticks between the starts of the first kCfStaggerBlocks workgroups' phases
   // (0: all start together), see k_cfpart
   int32_t stagger;
+  // 1: k_cfpart also where k_cfpart2 (two workgroups per CU) would run
+  int32_t one_wg;
 };
 constexpr int kCfStaggerBlocks = 256;   // one workgroup per CU in the first round (MI355X: 256 CUs)
 
@@ -706,6 +708,7 @@ void launch_derive(const DeriveArgs& a, bool vm, bool rowwise, hipStream_t s);
 void launch_mq_partition(const MqPartArgs& a, hipStream_t s);
 void launch_mq_walk(const MqWalkArgs& a, int nbuckets, hipStream_t s);
 void launch_cf_partition(const CfPartArgs& a, int64_t ntiles, hipStream_t s);
+bool cf_partition_2wg(const CfPartArgs& a);   // whether that launch is k_cfpart2's
 void launch_cf_walk(const CfWalkArgs& a, int nbuckets, hipStream_t s);
 void launch_keymap(const KeyMapArgs& a, hipStream_t s);
 void launch_route_keys(const RouteKeyArgs& a, hipStream_t s);

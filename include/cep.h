@@ -239,7 +239,8 @@ enum {
   CEP_K_ORDER = 4, CEP_K_AGG = 5, CEP_K_OTHER = 6,
   CEP_K_CF_PARTITION = 7, CEP_K_CF_WALK = 8,  /* closed-form fast path (k_cfpart / k_cfwalk) */
   CEP_K_HOT = 9,                              /* hot-key matching (hot.hip, one entry per chunk) */
-  CEP_K_MQ_PARTITION = 10, CEP_K_MQ_WALK = 11  /* multi-query groups (k_mqpart / k_mqwalk) */
+  CEP_K_MQ_PARTITION = 10, CEP_K_MQ_WALK = 11, /* multi-query groups (k_mqpart / k_mqwalk) */
+  CEP_K_CF_PARTITION_2WG = 12                 /* launches only: the CEP_K_CF_PARTITION launches that ran k_cfpart2 */
 };
 
 /* ---- plan-level calls (no device needed) ------------------------------ */
