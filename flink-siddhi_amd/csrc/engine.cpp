@@ -201,6 +201,23 @@ struct MqRT {
   DevBuf du;
 };
 
+// Windowed stream join (join_kernels.hip): both sides' kept-row lists (double
+// buffered: k_jointail moves the surviving rows into the other buffer), the
+// chunk's flag / probe scratch and the device state words.
+struct JoinRT {
+  int q = -1;
+  JoinArgs ja{};               // the plan's part of the kernel arguments
+  bool mark_vm = false;        // a side filter needs the interpreter
+  bool on_vm = false;          // `on` needs the interpreter
+  bool sel_vm = false;         // a select item is computed
+  int64_t chunk = 0;
+  int64_t list_cap[2] = {0, 0};
+  DevBuf list[2][2];           // [side][buffer]
+  int cur = 0;                 // buffer holding the current lists
+  DevBuf flag, bsum, boff, probe, pcnt, pbsum, pboff, st;
+  HostBuf total;               // pinned: the chunk's row total (read back before the emit pass)
+};
+
 struct TimedLaunch {
   int kind;
   hipEvent_t a, b;
@@ -229,6 +246,7 @@ struct cep_app {
   std::vector<OutStream> outs;
   std::vector<PatternRT> pats;
   std::vector<MqRT> mqs;          // multi-query groups
+  std::vector<JoinRT> joins;      // windowed stream joins
   std::vector<char> in_mq;        // per query: served by a multi-query group
   DevBuf tile_state, ticket, err;
   DevBuf route_arena, route_tcount, route_toffs, route_dcount;   // key shuffle (sender)
@@ -1333,6 +1351,64 @@ int create_runtime(cep_app* a) {
     rt.order_sensitive = p.within >= 0 && !agg && !(q.nfa && q.sequence);
     a->pats.push_back(rt);
   }
+  for (size_t qi = 0; qi < app.queries.size(); ++qi) {
+    const Query& q = app.queries[qi];
+    if (q.kind != Q_JOIN) continue;
+    const bool timed = q.join_side[0].win_kind == WIN_TIME || q.join_side[1].win_kind == WIN_TIME;
+    // A time window's rows are found by their position in the ts-ordered list
+    // of kept rows; with ts in any order Siddhi's window is positional (a late
+    // small ts sits behind a front row that blocks it) and the two differ.
+    if (timed && a->opt.ts_order != 1)
+      return fail(a, CEP_E_UNSUPPORTED, "a join with #window.time is not supported with ts_order = 0: the window "
+                                        "is a suffix of the side's rows only for non-decreasing timestamps "
+                                        "(set ts_order = 1)");
+    if (a->opt.key_stride > 1)
+      return fail(a, CEP_E_UNSUPPORTED, "a join is not supported with key_stride > 1: its windows are global "
+                                        "and cannot be sharded by key");
+    JoinRT rt;
+    rt.q = (int)qi;
+    JoinArgs& j = rt.ja;
+    j.stream[0] = q.a_stream;
+    j.stream[1] = q.b_stream;
+    for (int s = 0; s < 2; ++s) {
+      j.filter_prog[s] = q.join_side[s].filter.off;
+      j.filter_terms[s] = q.join_side[s].filter_terms;
+      j.win_kind[s] = q.join_side[s].win_kind;
+      j.win_param[s] = q.join_side[s].win_param;
+      rt.mark_vm |= j.filter_prog[s] >= 0 && j.filter_terms[s].n < 0;
+    }
+    j.nw = (int)q.rec_cols_a.size();
+    for (int w = 0; w < j.nw; ++w) j.rec[w] = q.rec_cols_a[w];
+    j.ew = 2 + j.nw;
+    j.on_prog = q.join_on.off;
+    j.nterms = std::max(0, q.join_nterms);
+    for (int i = 0; i < j.nterms; ++i) j.terms[i] = q.join_terms[i];
+    j.check_order = timed ? 1 : 0;
+    rt.on_vm = q.join_nterms < 0;
+    for (auto& it : q.select) rt.sel_vm |= it.src == SRC_VM;
+    int64_t chunk = std::max<int64_t>(a->opt.chunk_events, kJoinBlockRows);
+    chunk = std::min<int64_t>(chunk, kJoinMaxChunk);
+    chunk = (chunk / kJoinBlockRows) * kJoinBlockRows;
+    rt.chunk = chunk;
+    const int64_t nblk = chunk / kJoinBlockRows, npb = chunk / kJoinThreads;
+    bool ok = dev_ensure(&rt.flag, (size_t)chunk, a->stream, false) &&
+              dev_ensure(&rt.bsum, (size_t)nblk * 8, a->stream, false) &&
+              dev_ensure(&rt.boff, (size_t)nblk * 8, a->stream, false) &&
+              dev_ensure(&rt.probe, (size_t)chunk * 8, a->stream, false) &&
+              dev_ensure(&rt.pcnt, (size_t)chunk * 4, a->stream, false) &&
+              dev_ensure(&rt.pbsum, (size_t)npb * 4, a->stream, false) &&
+              dev_ensure(&rt.pboff, (size_t)npb * 4, a->stream, false) &&
+              dev_ensure(&rt.st, sizeof(JoinState), a->stream, false) && host_ensure(&rt.total, 64);
+    for (int s = 0; s < 2 && ok; ++s) {
+      // tail (length: N rows, time: kJoinTailCap) + one chunk's kept rows
+      rt.list_cap[s] = (j.win_kind[s] == WIN_LENGTH ? j.win_param[s] : (int64_t)kJoinTailCap) + chunk;
+      for (int b = 0; b < 2 && ok; ++b)
+        ok = dev_ensure(&rt.list[s][b], (size_t)rt.list_cap[s] * j.ew * 8, a->stream, false);
+    }
+    if (!ok) return fail(a, CEP_E_DEVICE, "out of device memory (join state)");
+    hipMemset(rt.st.p, 0, sizeof(JoinState));
+    a->joins.push_back(rt);
+  }
   {
     const int64_t none = INT64_MIN;
     if (!dev_ensure(&a->last_ts_dev, 64, a->stream, false) ||
@@ -2267,6 +2343,64 @@ int build_view(cep_app* a, int vi, const RowsArgs& rows, RowsArgs* out) {
   return CEP_OK;
 }
 
+// One join over a device batch, chunk by chunk (join_kernels.hip).  The number
+// of rows a chunk emits depends on the data (up to window size x rows), so it
+// is read back (8 bytes, one sync per chunk) between the count and the emit
+// pass and the output grows to hold exactly that.
+int run_join(cep_app* a, JoinRT& rt, const RowsArgs& rows_in) {
+  const Query& q = a->app.queries[rt.q];
+  OutStream& o = a->outs[a->app.output_index(q.out_stream)];
+  for (int64_t off = 0; off < rows_in.n; off += rt.chunk) {
+    JoinArgs j = rt.ja;
+    j.rows = rows_in;
+    j.rows.row0 = rows_in.row0 + off;
+    j.rows.n = std::min<int64_t>(rt.chunk, rows_in.n - off);
+    j.vm = {(const Ins*)a->code.p, (const uint64_t*)a->konst.p};
+    j.flag = (uint8_t*)rt.flag.p;
+    j.bsum = (uint32_t*)rt.bsum.p;
+    j.boff = (uint32_t*)rt.boff.p;
+    for (int s = 0; s < 2; ++s) {
+      j.list[s] = (uint64_t*)rt.list[s][rt.cur].p;
+      j.next[s] = (uint64_t*)rt.list[s][rt.cur ^ 1].p;
+      j.list_cap[s] = rt.list_cap[s];
+    }
+    j.probe = (uint64_t*)rt.probe.p;
+    j.pcnt = (uint32_t*)rt.pcnt.p;
+    j.pbsum = (uint32_t*)rt.pbsum.p;
+    j.pboff = (uint32_t*)rt.pboff.p;
+    j.st = (JoinState*)rt.st.p;
+    j.err = (unsigned int*)a->err.p;
+    j.out = out_args(o, q);
+    {
+      LaunchTimer t(a, CEP_K_JOIN);
+      launch_join_mark(j, rt.mark_vm, a->stream);
+    }
+    {
+      LaunchTimer t(a, CEP_K_JOIN);
+      if (rt.on_vm) a->launches[CEP_K_JOIN_VM]++;
+      launch_join_count(j, rt.on_vm, a->stream);
+    }
+    uint64_t* total = (uint64_t*)rt.total.p;
+    if (hipMemcpyAsync(total, &((JoinState*)rt.st.p)->total, 8, hipMemcpyDeviceToHost, a->stream) != hipSuccess ||
+        hipStreamSynchronize(a->stream) != hipSuccess)
+      return fail(a, CEP_E_DEVICE, "device failure during processing (join)");
+    if (*total > 0) {
+      o.bound += (int64_t)*total;
+      const int rc = ensure_out_cap(a, o, o.bound);
+      if (rc) return rc;
+      j.out = out_args(o, q);
+      LaunchTimer t(a, CEP_K_JOIN);
+      launch_join_emit(j, rt.on_vm, rt.sel_vm, a->stream);
+    }
+    {
+      LaunchTimer t(a, CEP_K_JOIN);
+      launch_join_tail(j, a->stream);
+    }
+    rt.cur ^= 1;
+  }
+  return CEP_OK;
+}
+
 int send_device_rows(cep_app* a, const RowsArgs& rows_in) {
   // query chaining: each view is built once per slice, before its first reader
   std::vector<RowsArgs> views(a->app.views.size());
@@ -2300,6 +2434,9 @@ int send_device_rows(cep_app* a, const RowsArgs& rows_in) {
     } else if (q.kind == Q_PATTERN || q.kind == Q_AGG) {
       for (auto& rt : a->pats)
         if (rt.q == (int)qi) rc = run_pattern(a, rt, rows, nullptr, 0, a->force_tolerant);
+    } else if (q.kind == Q_JOIN) {
+      for (auto& rt : a->joins)
+        if (rt.q == (int)qi) rc = run_join(a, rt, rows);
     }
     if (rc) return rc;
   }
@@ -2334,7 +2471,7 @@ int error_status(cep_app* a, unsigned int e) {
   if (!e) return CEP_OK;
   if (e & ERR_ORDER)   // root cause first: out-of-order input also defeats `within` pruning
     return fail(a, CEP_E_ARG, "events not in event-time order: `within` requires non-decreasing timestamps "
-                              "(so does group by with #window.time outside a partition)");
+                              "(so do group by with #window.time outside a partition and a join with #window.time)");
   // before the capacity flags: a time that did not fit its 32-bit field was
   // stored truncated, so partials and window rows stop expiring and the lists
   // overflow as a consequence
@@ -2356,6 +2493,9 @@ int error_status(cep_app* a, unsigned int e) {
   if (e & ERR_DERIVE)
     return fail(a, CEP_E_UNSUPPORTED, "a row passed the filters of two derived streams that one query reads "
                                       "(it would be two events of that query; make the producers' filters disjoint)");
+  if (e & ERR_JOIN_TAIL)
+    return fail(a, CEP_E_CAPACITY, "a join's #window.time held more than " + std::to_string(kJoinTailCap) +
+                                       " live rows at the end of a chunk (the oldest were dropped)");
   if (e & ERR_OUT_CAP) return fail(a, CEP_E_DEVICE, "output capacity exceeded");
   return fail(a, CEP_E_DEVICE, "device error flags " + std::to_string(e));
 }
@@ -2637,6 +2777,12 @@ void cep_destroy(cep_app* a) {
       dev_free(&g.toff[b]);
       dev_free(&g.chunk_base[b]);
     }
+  }
+  for (auto& jr : a->joins) {
+    for (DevBuf* b : {&jr.flag, &jr.bsum, &jr.boff, &jr.probe, &jr.pcnt, &jr.pbsum, &jr.pboff, &jr.st, &jr.list[0][0],
+                      &jr.list[0][1], &jr.list[1][0], &jr.list[1][1]})
+      dev_free(b);
+    host_free(&jr.total);
   }
   if (a->copy) hipStreamSynchronize(a->copy);
   for (auto& h : a->hs) {
@@ -3236,6 +3382,9 @@ void cep_free(void* p) { std::free(p); }
 //   the value -1 (0xffffffff: none), count x i64 partition value per dense slot.
 //   (version 5) u32 n_groups, per multi-query group: i64 key_capacity,
 //   u32 words per key, u32 n_live, n_live x { u32 key, words x u64 }.
+//   (version 6, written only by apps that hold a join; others still write 5)
+//   u32 n_joins, per join: u32 entry words, per side: u64 rows kept so far,
+//   u64 tail entries, tail x entry words u64 (the side's live rows, oldest first).
 // Versions 2 (no reorder section), 3 and 4 are still restored (apps without
 // multi-query groups).
 static uint64_t plan_hash(const CompiledApp& app) {
@@ -3252,6 +3401,15 @@ static uint64_t plan_hash(const CompiledApp& app) {
     if (q.win_kind == WIN_NONE) continue;
     const int64_t w[4] = {(int64_t)qi, q.win_kind, q.win_param, q.win_global ? 1 : 0};
     mix(w, sizeof(w));
+  }
+  // joins: sides, windows, carried columns (plans without a join hash as before)
+  for (size_t qi = 0; qi < app.queries.size(); ++qi) {
+    const Query& q = app.queries[qi];
+    if (q.kind != Q_JOIN) continue;
+    const int64_t w[8] = {-3, (int64_t)qi, q.a_stream, q.b_stream, q.join_side[0].win_kind, q.join_side[0].win_param,
+                          q.join_side[1].win_kind, q.join_side[1].win_param};
+    mix(w, sizeof(w));
+    for (int c : q.rec_cols_a) mix(&c, sizeof(c));
   }
   // query chaining (plans without derived streams hash as before)
   for (auto& d : app.derived) {
@@ -3277,7 +3435,8 @@ int cep_snapshot(cep_app* a, uint8_t** buf, size_t* len) {
   };
   const char magic[4] = {'C', 'E', 'P', 'S'};
   put(magic, 4);
-  uint32_t ver = 5;   // 3: + the event-time reorder buffer; 4: + pending counts (overflow runs); 5: + groups
+  // 3: + the event-time reorder buffer; 4: + pending counts (overflow runs); 5: + groups; 6: + joins
+  uint32_t ver = a->joins.empty() ? 5 : 6;
   put(&ver, 4);
   uint64_t h = plan_hash(a->app);
   put(&h, 8);
@@ -3386,6 +3545,25 @@ int cep_snapshot(cep_app* a, uint8_t** buf, size_t* len) {
       }
     }
   }
+  // (version 6) joins: each side's live rows (the list's tail) and counts
+  if (!a->joins.empty()) {
+    const uint32_t nj = (uint32_t)a->joins.size();
+    put(&nj, 4);
+    for (auto& jr : a->joins) {
+      JoinState st;
+      hipMemcpy(&st, jr.st.p, sizeof(st), hipMemcpyDeviceToHost);
+      const uint32_t ew = (uint32_t)jr.ja.ew;
+      put(&ew, 4);
+      for (int sd = 0; sd < 2; ++sd) {
+        const uint64_t tail = std::min<uint64_t>(st.tail[sd], (uint64_t)jr.list_cap[sd]);
+        put(&st.kept[sd], 8);
+        put(&tail, 8);
+        std::vector<uint64_t> rows((size_t)tail * ew);
+        if (tail) hipMemcpy(rows.data(), jr.list[sd][jr.cur].p, rows.size() * 8, hipMemcpyDeviceToHost);
+        put(rows.data(), rows.size() * 8);
+      }
+    }
+  }
   *buf = (uint8_t*)std::malloc(out.size());
   if (!*buf) return fail(a, CEP_E_DEVICE, "out of host memory");
   std::memcpy(*buf, out.data(), out.size());
@@ -3407,7 +3585,7 @@ int cep_restore(cep_app* a, const uint8_t* buf, size_t len) {
   uint64_t h;
   int64_t ev;
   uint32_t np;
-  if (!get(magic, 4) || std::memcmp(magic, "CEPS", 4) || !get(&ver, 4) || ver < 2 || ver > 5 || !get(&h, 8) ||
+  if (!get(magic, 4) || std::memcmp(magic, "CEPS", 4) || !get(&ver, 4) || ver < 2 || ver > 6 || !get(&h, 8) ||
       !get(&ev, 8) || !get(&np, 4))
     return fail(a, CEP_E_STATE, "not a libcep snapshot");
   if (h != plan_hash(a->app) || np != a->pats.size())
@@ -3557,6 +3735,32 @@ int cep_restore(cep_app* a, const uint8_t* buf, size_t len) {
     return fail(a, CEP_E_STATE, "snapshot has no multi-query group state (version < 5): "
                                 "create the runtime with CEP_NO_MQ=1 to restore it on per-query state");
   }
+  // (version 6) joins
+  struct JoinSnap {
+    uint64_t kept[2] = {0, 0}, tail[2] = {0, 0};
+    std::vector<uint64_t> rows[2];
+  };
+  std::vector<JoinSnap> js(a->joins.size());
+  if (ver >= 6) {
+    uint32_t nj;
+    if (!get(&nj, 4) || nj != a->joins.size()) return fail(a, CEP_E_STATE, "snapshot joins do not match");
+    for (size_t ji = 0; ji < a->joins.size(); ++ji) {
+      const JoinRT& jr = a->joins[ji];
+      uint32_t ew;
+      if (!get(&ew, 4) || ew != (uint32_t)jr.ja.ew)
+        return fail(a, CEP_E_STATE, "snapshot geometry differs from this runtime (join rows)");
+      for (int sd = 0; sd < 2; ++sd) {
+        if (!get(&js[ji].kept[sd], 8) || !get(&js[ji].tail[sd], 8)) return fail(a, CEP_E_STATE, "truncated snapshot");
+        const uint64_t tail = js[ji].tail[sd];
+        const uint64_t max_tail = jr.ja.win_kind[sd] == WIN_LENGTH ? (uint64_t)jr.ja.win_param[sd] : (uint64_t)kJoinTailCap;
+        if (tail > max_tail || tail * ew > (len - off) / 8) return fail(a, CEP_E_STATE, "corrupt snapshot (join rows)");
+        js[ji].rows[sd].resize((size_t)tail * ew);
+        get(js[ji].rows[sd].data(), js[ji].rows[sd].size() * 8);
+      }
+    }
+  } else if (!a->joins.empty()) {
+    return fail(a, CEP_E_STATE, "snapshot has no join state (version < 6)");
+  }
   // Phase 2: commit (device allocations first, so a failure leaves the
   // runtime as it was)
   auto& r = a->ro;
@@ -3613,11 +3817,27 @@ int cep_restore(cep_app* a, const uint8_t* buf, size_t len) {
   }
   for (size_t gi = 0; gi < a->mqs.size(); ++gi)
     hipMemcpy(a->mqs[gi].state.p, mst[gi].data(), mst[gi].size() * 8, hipMemcpyHostToDevice);
+  for (size_t ji = 0; ji < a->joins.size(); ++ji) {
+    JoinRT& jr = a->joins[ji];
+    JoinState st{};
+    for (int sd = 0; sd < 2; ++sd) {
+      st.kept[sd] = js[ji].kept[sd];
+      st.tail[sd] = st.n[sd] = js[ji].tail[sd];
+      if (!js[ji].rows[sd].empty())
+        hipMemcpy(jr.list[sd][jr.cur].p, js[ji].rows[sd].data(), js[ji].rows[sd].size() * 8, hipMemcpyHostToDevice);
+    }
+    hipMemcpy(jr.st.p, &st, sizeof(st), hipMemcpyHostToDevice);
+  }
   a->events_in = ev;
   return CEP_OK;
 }
 
 int cep_record_words(cep_app* a) {
+  if (a && !a->joins.empty()) {
+    fail(a, CEP_E_UNSUPPORTED, "key shuffle of an app that holds a join is not supported: its windows are global, "
+                               "not per key");
+    return -CEP_E_UNSUPPORTED;
+  }
   if (!a || a->pats.size() != 1) return -CEP_E_UNSUPPORTED;
   return a->pats[0].pa.rec_words + 1;   // wide record: [hdr, seq, ts, carried...]
 }
@@ -3638,6 +3858,9 @@ static int route_batch(cep_app* a, const cep_batch* b, int world, int64_t seq0, 
   if (!a->app.derived.empty())
     return fail(a, CEP_E_UNSUPPORTED, "key shuffle of an app with query chaining (derived streams) is not supported: "
                                       "the sender needs the key in source columns");
+  if (!a->joins.empty())
+    return fail(a, CEP_E_UNSUPPORTED, "key shuffle of an app that holds a join is not supported: its windows are "
+                                      "global, not per key");
   if (a->pats.size() != 1 || a->app.queries.size() != 1)
     return fail(a, CEP_E_UNSUPPORTED, "key shuffle needs an app with exactly one keyed pattern");
   PatternRT& rt = a->pats[0];
@@ -3792,6 +4015,9 @@ static int row_route_plan(cep_app* a, int32_t (&kc)[8], int* layout) {
   const CompiledApp& app = a->app;
   const int ni = (int)app.inputs.size();
   if (ni > 8) return fail(a, CEP_E_UNSUPPORTED, "row shuffle supports at most 8 input streams");
+  if (!a->joins.empty())
+    return fail(a, CEP_E_UNSUPPORTED, "row shuffle of an app that holds a join is not supported: its windows are "
+                                      "global, not per key");
   for (int i = 0; i < 8; ++i) kc[i] = -2;
   auto need = [&](int s, int col) -> int {
     if (s < 0 || s >= ni) return CEP_OK;

@@ -8,7 +8,8 @@
 //   query      := 'from' input ['select' ('*' | item {',' item})]
 //                 ['group' 'by' attr {',' attr}] ['having' expr]
 //                 'insert' [('all'|'current'|'expired') 'events'] 'into' ID
-//   input      := ID {'[' expr ']'} [window] ['as' ID]
+//   input      := side | side ['inner'] 'join' side ['on' expr]   (windowed stream join)
+//   side       := ID {'[' expr ']'} [window] ['as' ID]
 //   window     := '#' 'window' '.' ('length' '(' INT ')' | 'time' '(' (INT | time) ')')
 //               | state ('->' state)* ['within' time]          (patterns)
 //   state      := ['every'] ID '=' ID ['[' expr ']']
@@ -203,6 +204,13 @@ struct QueryAst {
   int win_kind = WIN_NONE;     // sliding window after the filters
   int64_t win_param = 0;       // rows (length) / ms (time)
   std::string win_events;      // window queries: the 'insert <x> events' keyword ("" = none given)
+  // windowed stream join: the second side and the `on` condition (null: none)
+  bool join = false;
+  std::string stream2, alias2;
+  std::vector<ExprP> filters2;
+  int win_kind2 = WIN_NONE;
+  int64_t win_param2 = 0;
+  ExprP on;
   std::vector<State> states;
   int64_t within = -1;
   bool select_all = true;
@@ -366,27 +374,27 @@ class Parser {
       fail(CEP_E_UNSUPPORTED, "inner streams (from #" + peek(1).v + ") are not supported");
     if (!is_state_start()) {
       q.single = true;
-      q.stream = ident();
-      while (true) {
-        if (accept(TK_OP, "[")) {
-          q.filters.push_back(expr());
-          expect(TK_OP, "]");
-        } else if (peek().k == TK_OP && peek().v == "#") {
-          if (q.win_kind != WIN_NONE)
-            fail(CEP_E_UNSUPPORTED, "a second window / stream function after #window is not supported");
-          window(&q);
-          if (peek().k == TK_OP && peek().v == "[")
-            fail(CEP_E_UNSUPPORTED, "a filter after the window (#window.x(..)[f]) is not supported");
-        } else {
-          break;
-        }
+      side(&q.stream, &q.alias, &q.filters, &q.win_kind, &q.win_param);
+      // joins: inner joins of two windowed streams compile (compile_join);
+      // every other join form is refused here by name
+      auto word = [&](const char* w) { return peek().k == TK_ID && lower(peek().v) == w; };
+      if (peek().k == TK_KW && peek().v == "unidirectional")
+        fail(CEP_E_UNSUPPORTED, "unidirectional joins are not supported");
+      if (word("left") || word("right") || word("full") || word("outer"))
+        fail(CEP_E_UNSUPPORTED, "outer joins (" + lower(peek().v) + " ... join) are not supported, only the inner join");
+      if (word("inner") && peek(1).k == TK_KW && peek(1).v == "join") next();
+      if (accept(TK_KW, "join")) {
+        q.join = true;
+        if (peek().k == TK_OP && peek().v == "#")
+          fail(CEP_E_UNSUPPORTED, "inner streams (join #" + peek(1).v + ") are not supported");
+        side(&q.stream2, &q.alias2, &q.filters2, &q.win_kind2, &q.win_param2);
+        if (peek().k == TK_KW && peek().v == "unidirectional")
+          fail(CEP_E_UNSUPPORTED, "unidirectional joins are not supported");
+        if (accept(TK_KW, "on")) q.on = expr();
+        if (peek().k == TK_KW && peek().v == "within")
+          fail(CEP_E_UNSUPPORTED, "`within` on a join is not supported");
+        if (word("per")) fail(CEP_E_UNSUPPORTED, "`per` on a join is not supported");
       }
-      if (accept(TK_KW, "as")) q.alias = ident();
-      if ((peek().k == TK_KW && (peek().v == "join" || peek().v == "unidirectional")) ||
-          (peek().k == TK_ID && (lower(peek().v) == "left" || lower(peek().v) == "right" ||
-                                 lower(peek().v) == "full" || lower(peek().v) == "inner" ||
-                                 lower(peek().v) == "outer")))
-        fail(CEP_E_UNSUPPORTED, "joins are not supported");
     } else {
       q.single = false;
       q.states.push_back(state());
@@ -435,7 +443,7 @@ class Parser {
       expect(TK_KW, "events");
       // only a window has expired events: non-window queries emit the same
       // rows whatever the keyword
-      if (q.win_kind != WIN_NONE) q.win_events = ev;
+      if (q.win_kind != WIN_NONE || q.join) q.win_events = ev;
     }
     expect(TK_KW, "into");
     if (peek().k == TK_OP && peek().v == "#")
@@ -444,8 +452,28 @@ class Parser {
     return q;
   }
 
+  // One input side: `Stream[filter]*[#window.x(..)] [as alias]`.
+  void side(std::string* stream, std::string* alias, std::vector<ExprP>* filters, int* win_kind, int64_t* win_param) {
+    *stream = ident();
+    while (true) {
+      if (accept(TK_OP, "[")) {
+        filters->push_back(expr());
+        expect(TK_OP, "]");
+      } else if (peek().k == TK_OP && peek().v == "#") {
+        if (*win_kind != WIN_NONE)
+          fail(CEP_E_UNSUPPORTED, "a second window / stream function after #window is not supported");
+        window(win_kind, win_param);
+        if (peek().k == TK_OP && peek().v == "[")
+          fail(CEP_E_UNSUPPORTED, "a filter after the window (#window.x(..)[f]) is not supported");
+      } else {
+        break;
+      }
+    }
+    if (accept(TK_KW, "as")) *alias = ident();
+  }
+
   // '#window.length(N)' / '#window.time(T)'; every other '#...' is refused.
-  void window(QueryAst* q) {
+  void window(int* kind, int64_t* param) {
     expect(TK_OP, "#");
     Token t = next();
     if (!(t.k == TK_KW && t.v == "window")) {
@@ -475,8 +503,8 @@ class Parser {
     }
     expect(TK_OP, ")");
     if (v < 1) fail(CEP_E_PARSE, "#window." + name + " needs a constant >= 1");
-    q->win_kind = name == "length" ? WIN_LENGTH : WIN_TIME;
-    q->win_param = v;
+    *kind = name == "length" ? WIN_LENGTH : WIN_TIME;
+    *param = v;
   }
 
   int64_t time_const() {
@@ -1679,6 +1707,136 @@ void compile_pattern(CompiledApp* app, QueryAst& q) {
   app->queries.push_back(out);
 }
 
+// Windowed stream join: `from A[f]#window.wa as a join
+// B[g]#window.wb as b on C select ... insert into O`.  Bound like a two-state
+// pattern (state 0 = the A side, state 1 = the B side); both sides share one
+// definition, so one carried-column list (rec_cols_a) serves either side's
+// kept rows.
+void compile_join(CompiledApp* app, QueryAst& q) {
+  const int sa = app->input_index(q.stream), sb = app->input_index(q.stream2);
+  if (sa < 0) fail(CEP_E_UNDEFINED_STREAM, "stream " + q.stream + " is not defined");
+  if (sb < 0) fail(CEP_E_UNDEFINED_STREAM, "stream " + q.stream2 + " is not defined");
+  if (q.partitioned) fail(CEP_E_UNSUPPORTED, "a join inside `partition with` is not supported");
+  if (sa == sb) fail(CEP_E_UNSUPPORTED, "a self-join (join of stream " + q.stream + " with itself) is not supported");
+  if (q.win_kind == WIN_NONE || q.win_kind2 == WIN_NONE)
+    fail(CEP_E_UNSUPPORTED, "a join side without a window is not supported: both sides need #window.length(N) "
+                            "or #window.time(T)");
+  const StreamSchema& A = app->inputs[sa];
+  const StreamSchema& B = app->inputs[sb];
+  bool same = A.attrs.size() == B.attrs.size();
+  for (size_t c = 0; same && c < A.attrs.size(); ++c)
+    same = A.attrs[c].name == B.attrs[c].name && A.attrs[c].type == B.attrs[c].type;
+  if (!same)
+    fail(CEP_E_UNSUPPORTED, "a join of streams with different definitions (" + A.id + ", " + B.id +
+                                ") is not supported");
+  if (!q.win_events.empty() && q.win_events != "current")
+    fail(CEP_E_UNSUPPORTED, "insert " + q.win_events + " events on a join is not supported "
+                                "(only current events are emitted)");
+  if (!q.group_by.empty() || q.having) fail(CEP_E_UNSUPPORTED, "group by / having on a join is not supported");
+  for (int s = 0; s < 2; ++s) {
+    const int kind = s ? q.win_kind2 : q.win_kind;
+    const int64_t param = s ? q.win_param2 : q.win_param;
+    if (kind == WIN_LENGTH && param > 255)
+      fail(CEP_E_UNSUPPORTED, "a join over #window.length(" + std::to_string(param) +
+                                  ") is not supported: at most 255 rows per side");
+  }
+  if (q.select_all) fail(CEP_E_PARSE, "join query needs an explicit select");
+  Query out;
+  out.kind = Q_JOIN;
+  out.out_stream = q.out;
+  out.a_stream = sa;
+  out.b_stream = sb;
+  Ctx c;
+  c.mode = Ctx::PATTERN;
+  c.states = {&A, &B};
+  c.aliases = {q.alias.empty() ? q.stream : q.alias, q.alias2.empty() ? q.stream2 : q.alias2};
+  if (c.aliases[0] == c.aliases[1]) fail(CEP_E_PARSE, "duplicate alias " + c.aliases[0] + " in join");
+  // side filters: over the side's own row
+  Loader raw{[](const Expr& e) { return std::make_pair((uint8_t)OP_LDCOL, (uint32_t)e.col); }};
+  for (int s = 0; s < 2; ++s) {
+    auto& fs = s ? q.filters2 : q.filters;
+    for (auto& f : fs) {
+      if (has_call(f)) fail(CEP_E_PARSE, "aggregate in a filter");
+      c.cur_state = s;
+      bind_expr(f, c, app);
+      if (f->t != T_BOOL) fail(CEP_E_PARSE, "filter condition must be bool");
+      std::vector<std::pair<int, int>> refs;
+      collect_refs(f, &refs);
+      for (auto& r : refs)
+        if (r.first != s) fail(CEP_E_PARSE, "a join side's filter reads the other side (" + c.aliases[r.first] + ")");
+    }
+    Query::JoinSide& js = out.join_side[s];
+    js.filter = compile_and(app, fs, raw);
+    js.filter_terms = lower_terms(fs);
+    js.win_kind = s ? q.win_kind2 : q.win_kind;
+    js.win_param = s ? q.win_param2 : q.win_param;
+  }
+  c.cur_state = -1;
+  if (q.on) {
+    if (has_call(q.on)) fail(CEP_E_UNSUPPORTED, "aggregates in a join's `on` condition are not supported");
+    bind_expr(q.on, c, app);
+    if (q.on->t != T_BOOL) fail(CEP_E_PARSE, "join `on` condition must be bool");
+  }
+  std::set<std::string> names;
+  for (auto& it : q.select) {
+    if (has_call(it.e)) fail(CEP_E_UNSUPPORTED, "aggregates in a join's select are not supported");
+    bind_expr(it.e, c, app);
+    if (it.e->t == T_OBJECT) fail(CEP_E_UNSUPPORTED, "object attributes in select");
+    if (!names.insert(it.name).second) fail(CEP_E_PARSE, "duplicate output attribute " + it.name);
+  }
+  // kept rows carry only the columns `on` and the select list read
+  auto rec_word = [&](int col) { return index_of(out.rec_cols_a, col, true); };
+  Loader jl{[&](const Expr& e) {
+    return std::make_pair((uint8_t)(e.state == 0 ? OP_LDCOL : OP_LDCAP), (uint32_t)rec_word(e.col));
+  }};
+  out.join_nterms = 0;
+  if (q.on) {
+    // direct form: a conjunction of `a.x op b.y` between plain attributes of one type
+    std::vector<ExprP> atoms;
+    flatten(q.on, "and", &atoms);
+    bool direct = (int)atoms.size() <= kMaxTerms;
+    for (size_t i = 0; direct && i < atoms.size(); ++i) {
+      const ExprP& e = atoms[i];
+      const bool cmp = e->k == Expr::BIN && (e->op == "==" || e->op == "!=" || e->op == "<" || e->op == "<=" ||
+                                             e->op == ">" || e->op == ">=");
+      direct = cmp && e->args[0]->k == Expr::ATTR && e->args[1]->k == Expr::ATTR && e->args[0]->idx == -1 &&
+               e->args[1]->idx == -1 && e->args[0]->state != e->args[1]->state && e->args[0]->t == e->args[1]->t &&
+               e->args[0]->t != T_OBJECT;
+    }
+    if (direct) {
+      for (auto& e : atoms) {
+        const bool flip = e->args[0]->state == 1;   // written `b.y op a.x`
+        const ExprP& ea = e->args[flip ? 1 : 0];
+        const ExprP& eb = e->args[flip ? 0 : 1];
+        JoinTerm& t = out.join_terms[out.join_nterms++];
+        t.wa = rec_word(ea->col);
+        t.wb = rec_word(eb->col);
+        t.op = cmp_op(e->op, flip);
+        t.type = (ea->t == T_BOOL || ea->t == T_STRING) ? T_INT : ea->t;
+      }
+    } else {
+      out.join_nterms = -1;
+    }
+    CodeGen cg(app, jl);
+    out.join_on = cg.compile(q.on);
+  }
+  for (auto& it : q.select) {
+    OutItem oi;
+    oi.name = it.name;
+    oi.type = it.e->t;
+    CodeGen cg(app, jl);
+    oi.prog = cg.compile(it.e);
+    oi.src = direct_source(app, oi.prog);   // SRC_REC + w: A-side word, SRC_CAP + w: B-side word
+    out.select.push_back(oi);
+  }
+  if ((int)out.rec_cols_a.size() > kMaxCaps)
+    fail(CEP_E_UNSUPPORTED, "a join reading more than " + std::to_string(kMaxCaps) +
+                                " attributes in `on` and select is not supported");
+  out.rec_cols_b = out.rec_cols_a;
+  add_output(app, q.out, out.select);
+  app->queries.push_back(out);
+}
+
 bool same_types(const StreamSchema& x, const StreamSchema& y) {
   if (x.attrs.size() != y.attrs.size()) return false;
   for (size_t c = 0; c < x.attrs.size(); ++c)
@@ -1699,6 +1857,9 @@ void resolve_chains(CompiledApp* app) {
     const int m = app->input_index(q.out_stream);
     if (m < 0 || !read[m]) continue;   // an output nobody reads
     const std::string what = "stream " + q.out_stream + " is read by another query: its producer ";
+    if (q.kind == Q_JOIN)
+      fail(CEP_E_UNSUPPORTED, what + "must be a plain filter / projection query, not a join (chaining a join's "
+                                     "output is not supported)");
     if (q.kind == Q_PATTERN)
       fail(CEP_E_UNSUPPORTED, what + "must be a plain filter / projection query, not a pattern or sequence");
     if (q.win_kind != WIN_NONE)
@@ -1754,6 +1915,8 @@ void resolve_chains(CompiledApp* app) {
         up(s);
       }
     if (!any) continue;
+    if (q.kind == Q_JOIN)
+      fail(CEP_E_UNSUPPORTED, "a join that reads a derived stream (the output of another query) is not supported");
     for (int s : reads)
       if (anc[s])
         fail(CEP_E_UNSUPPORTED, "one query reading a derived stream and stream " + app->inputs[s].id +
@@ -1847,10 +2010,12 @@ int compile_app(const std::string& text, CompiledApp* out, std::string* err,
     Parser(text).parse(&app.inputs, &qs);
     for (auto& q : qs) {
       if (q.single) app.read_ids.push_back(q.stream);
+      if (q.join) app.read_ids.push_back(q.stream2);
       for (auto& st : q.states) app.read_ids.push_back(st.stream);
     }
     for (auto& q : qs) {
-      if (q.single) compile_single(&app, q);
+      if (q.join) compile_join(&app, q);
+      else if (q.single) compile_single(&app, q);
       else compile_pattern(&app, q);
     }
     resolve_chains(&app);

@@ -5,8 +5,8 @@
 //   SiddhiCompiler.parse                 (SiddhiExecutionPlanner.java:76)
 //   SiddhiAppRuntime.getStreamDefinitionMap for output-type inference
 //                                         (SiddhiTypeFactory.java:64-112)
-// Unsupported-but-valid SiddhiQL (joins, windows other than sliding
-// #window.length / #window.time aggregates, tables, extensions) fails
+// Unsupported-but-valid SiddhiQL (outer / unidirectional joins, windows other
+// than sliding #window.length / #window.time, tables, extensions) fails
 // with CEP_E_UNSUPPORTED so the Java shim can fall back to real Siddhi.
 #pragma once
 #include <map>
@@ -32,7 +32,7 @@ struct StreamSchema {
   }
 };
 
-enum QueryKind { Q_FILTER = 0, Q_PATTERN = 1, Q_AGG = 2 };
+enum QueryKind { Q_FILTER = 0, Q_PATTERN = 1, Q_AGG = 2, Q_JOIN = 3 };
 
 
 struct AggSpec {
@@ -111,6 +111,23 @@ struct Query {
   std::vector<NState> nstates;
   std::vector<NCap> ncaps;
   std::vector<int> key_col_s;    // per input stream handle: partition key column (-1)
+
+  // ---- windowed stream join `A[f]#window.x as a join B[g]#window.y as b on C`
+  // (Q_JOIN, join_kernels.hip): a_stream / b_stream are the two sides; both
+  // have one definition, so kept rows of either side carry rec_cols_a.  The
+  // side filters read raw columns; join_on and the select programs read the
+  // A-side row's carried word w as LDCOL w (SRC_REC + w) and the B-side row's
+  // as LDCAP w (SRC_CAP + w), whichever of the two rows triggered the match.
+  struct JoinSide {
+    Prog filter;                 // conjunction of the side's filters, invalid = true
+    TermList filter_terms;
+    int win_kind = WIN_NONE;
+    int64_t win_param = 0;       // rows (length) / ms (time)
+  };
+  JoinSide join_side[2];
+  Prog join_on;                  // invalid: no `on` (every pair joins)
+  int join_nterms = -1;          // >= 0: `on` as direct comparisons (join_terms), -1: interpreter only
+  JoinTerm join_terms[kMaxTerms];
 
   // ---- query chaining (derive.hip): the query reads derived streams through
   // view `view` of CompiledApp::views (-1: it reads the batch as sent)

@@ -78,6 +78,7 @@ enum : uint32_t {
   ERR_TS_SPAN = 128u,
   ERR_SHUFFLE_CAP = 256u,    // padded key shuffle: an owner segment held more than seg_cap records
   ERR_DERIVE = 512u,         // query chaining: a row passed the filters of two derived streams one query reads
+  ERR_JOIN_TAIL = 1024u,     // join: a time window held more than kJoinTailCap live rows at a chunk's end
 };
 
 // Per-key state header: pending count (bits 0-7, <= S) | started << 8 |
@@ -311,6 +312,69 @@ struct WinArgs {
   OutArgs out;
   unsigned int* err;
 };
+
+// ------------------------------------- windowed stream joins (join_kernels.hip) --
+// `from A[f]#window.wa as a join B[g]#window.wb as b on C select ...` (DESIGN
+// §10).  Per side a device list of kept rows in arrival order, entry =
+// entry_words u64: [ts, arrival number, carried words (JoinArgs::rec)].  The
+// first JoinState::tail entries survive from earlier chunks and batches; a
+// chunk appends its kept rows behind them.  Each kept row is also a probe
+// (arrival order over both sides):
+//   own list index (31) | `hi`, the other list's entry count before the row (31) << 31 | side << 62
+// and joins the other list's entries [lo, hi): lo = hi - N (length) or the
+// lower bound of ts + T > the row's ts (time; the lists are ts-ordered then).
+constexpr int kJoinThreads = 256;
+constexpr int kJoinItems = 4;                  // consecutive rows per lane of the mark / append passes
+constexpr int kJoinBlockRows = kJoinThreads * kJoinItems;
+constexpr int kJoinTile = 256;                 // window entries staged in LDS at a time
+constexpr int kJoinMaxLen = 255;               // rows of a length window
+constexpr int kJoinTailCap = 65536;            // live rows of a time window carried across chunks
+constexpr int64_t kJoinMaxChunk = 1 << 18;     // rows per chunk (list arenas: tail + chunk entries)
+
+struct JoinState {              // device words of one join
+  uint64_t n[2];                // entries of each side's list (tail + this chunk's kept rows)
+  uint64_t tail[2];             // entries surviving from earlier chunks (the list's front)
+  uint64_t kept[2];             // rows kept so far
+  uint64_t nprobe;              // probes of this chunk
+  uint64_t total;               // rows this chunk emits
+  uint64_t out_base;            // first output row of this chunk
+  uint64_t pad[7];
+};
+
+struct JoinArgs {
+  RowsArgs rows;
+  VmArgs vm;
+  int32_t stream[2];            // input handle of the A / B side
+  int32_t filter_prog[2];       // -1: every row of the side is kept
+  TermList filter_terms[2];     // n >= 0: interpreter-free filter
+  int32_t win_kind[2];
+  int64_t win_param[2];
+  int32_t nw;                   // carried words per entry
+  int32_t rec[kMaxCaps];        // their columns
+  int32_t ew;                   // entry words: 2 + nw
+  int32_t on_prog;              // -1: no `on`
+  int32_t nterms;               // direct `on` terms (k_joinprobe<false, ..>)
+  JoinTerm terms[kMaxTerms];
+  int32_t check_order;          // 1: some side has a time window (ts must not descend)
+  uint8_t* flag;                // per chunk row: 0 not kept, 1 A side, 2 B side
+  uint32_t* bsum;               // [blocks][2] kept rows per mark block and side
+  uint32_t* boff;               // [blocks][2] their exclusive prefix over the chunk
+  uint64_t* list[2];            // current lists
+  uint64_t* next[2];            // the other buffers (k_jointail moves the tails there)
+  int64_t list_cap[2];          // entries per list buffer
+  uint64_t* probe;              // [chunk rows]
+  uint32_t* pcnt;               // [chunk rows] matches per probe
+  uint32_t* pbsum;              // [probe blocks] matches per probe block
+  uint32_t* pboff;              // [probe blocks] exclusive prefix
+  JoinState* st;
+  OutArgs out;
+  unsigned int* err;
+};
+
+void launch_join_mark(const JoinArgs& a, bool vm, hipStream_t s);     // k_joinmark, k_joinscan, k_joinappend
+void launch_join_count(const JoinArgs& a, bool vm, hipStream_t s);    // k_joinprobe count pass + offsets
+void launch_join_emit(const JoinArgs& a, bool vm_on, bool vm_sel, hipStream_t s);
+void launch_join_tail(const JoinArgs& a, hipStream_t s);
 
 // ------------------------------------------ closed-form fast path (cf_kernels.hip) --
 // `every s1=A[f] -> s2=B[g] within W` with f / g on the events' own columns,

@@ -101,6 +101,14 @@ enum AggFn { AGG_SUM = 0, AGG_COUNT = 1, AGG_AVG = 2, AGG_MIN = 3, AGG_MAX = 4 }
 // Sliding window of a group-by query (Query::win_kind, WinArgs::kind).
 enum WinKind : int32_t { WIN_NONE = 0, WIN_LENGTH = 1, WIN_TIME = 2 };
 
+// Interpreter-free `on` condition of a windowed stream join: a conjunction of
+// up to kMaxTerms comparisons `a.x op b.y` between plain attributes of one
+// type; wa / wb index the carried words of the A-side / B-side row.
+struct JoinTerm {
+  int32_t wa, wb;
+  int32_t op, type;
+};
+
 // Role bits carried in partition records (pattern path).
 enum : uint32_t {
   ROLE_A = 1u,        // event passes the start state's filter f

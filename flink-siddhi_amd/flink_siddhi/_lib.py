@@ -30,7 +30,7 @@ NUMPY_DTYPES = {INT: "int32", LONG: "int64", FLOAT: "float32",
                 DOUBLE: "float64", BOOL: "uint8", STRING: "int32"}
 
 (K_FILTER, K_PARTITION, K_WALK, K_ROUTE, K_ORDER, K_AGG, K_OTHER, K_CF_PARTITION, K_CF_WALK, K_HOT,
- K_MQ_PARTITION, K_MQ_WALK, K_CF_PARTITION_2WG) = range(13)
+ K_MQ_PARTITION, K_MQ_WALK, K_CF_PARTITION_2WG, K_JOIN, K_JOIN_VM) = range(15)
 
 
 # ---- exceptions mirroring the reference ---------------------------------

@@ -39,8 +39,35 @@
  * partition is accepted with ts_order = 1 only (cep_create: CEP_E_UNSUPPORTED
  * otherwise); `group by k` + #window.length outside a partition, a filter
  * after the window, every other #window.x / stream function, `insert expired /
- * all events` and windows on pattern states or joins are CEP_E_UNSUPPORTED.
+ * all events` and windows on pattern states are CEP_E_UNSUPPORTED.
  * A window query without aggregates is the plain projection.
+ *
+ * Join queries: `from A[f]#window.wa [as a] join B[g]#window.wb [as b] on C
+ * select ... insert [current events] into O`, an inner join of two different
+ * streams with identical definitions, each side behind #window.length(N) (1
+ * <= N <= 255) or #window.time(T), combined freely.  A side is named by its
+ * alias, or by its stream when it has none.  Per row e of a side that passes
+ * the side's filter, in arrival order over both streams: the other side's
+ * window as it stands when e arrives (of its kept rows before e, the last N,
+ * or those with ts + T > e.ts), oldest first; for each of its rows where C
+ * holds (a.* the A-side row, b.* the B-side row) one output row with e's ts
+ * and arrival number; then e enters its own side's window (upstream Siddhi 4.x
+ * semantics).  Both windows are global (one per side and
+ * query).  `on` is any bool expression over both sides, the select list any
+ * expressions over both sides (no aggregates, no `select *`).  A join with a
+ * time window needs ts_order = 1 (cep_create: CEP_E_UNSUPPORTED otherwise; a
+ * ts descent then fails the next flush with CEP_E_ARG); two length windows
+ * take ts in any order.  A time window that holds more than 65536 live rows
+ * at the end of a chunk fails the next flush with CEP_E_CAPACITY.  The number
+ * of rows a chunk emits is read back before they are written (one 8-byte
+ * readback per chunk of at most 2^18 rows), so cep_send_batch() of a join app
+ * waits for the device once per chunk.  CEP_E_UNSUPPORTED (the message names
+ * the join): streams with different definitions, a side without a window, a
+ * self-join, left / right / full / outer and unidirectional joins, `within` /
+ * `per`, aggregates, group by, having, a join inside `partition with`, a join
+ * that reads a derived stream or whose output another query reads, `insert
+ * expired / all events`; at cep_create: key_stride > 1 (global windows cannot
+ * be sharded by key); at the call: cep_route_* of an app that holds a join.
  *
  * Hot-key probe: a keyed `every A -> B` runtime on the closed-form path
  * walks its first 2^20 rows as a short chunk and waits for it once inside
@@ -66,15 +93,17 @@ extern "C" {
  *                              SiddhiOperatorContext.java:151)
  *   CEP_E_DUPLICATED_STREAM-> exception/DuplicatedStreamException.java:20
  *   CEP_E_UNSUPPORTED      -> valid SiddhiQL outside the engine subset
- *                             (joins, tables, windows other than the sliding
- *                             #window.length / #window.time aggregates
- *                             below): shim falls back to real Siddhi
+ *                             (tables, outer / unidirectional joins and the
+ *                             other join forms listed above, windows other
+ *                             than sliding #window.length / #window.time):
+ *                             shim falls back to real Siddhi
  *   CEP_E_ARG              -> IllegalArgumentException
  *                             (operator/StreamOutputHandler.java:89)
  *   CEP_E_DEVICE           -> HIP failure / no gfx950 device
  *   CEP_E_CAPACITY         -> per-key pending-state or key-space capacity
  *                             exceeded (raise cep_options.pending_slots /
- *                             pending_pool_log2 / key_capacity)
+ *                             pending_pool_log2 / key_capacity); a join's time
+ *                             window past its 65536 live rows
  *   CEP_E_STATE            -> snapshot incompatible with this plan
  */
 enum {
@@ -240,7 +269,9 @@ enum {
   CEP_K_CF_PARTITION = 7, CEP_K_CF_WALK = 8,  /* closed-form fast path (k_cfpart / k_cfwalk) */
   CEP_K_HOT = 9,                              /* hot-key matching (hot.hip, one entry per chunk) */
   CEP_K_MQ_PARTITION = 10, CEP_K_MQ_WALK = 11, /* multi-query groups (k_mqpart / k_mqwalk) */
-  CEP_K_CF_PARTITION_2WG = 12                 /* launches only: the CEP_K_CF_PARTITION launches that ran k_cfpart2 */
+  CEP_K_CF_PARTITION_2WG = 12,                /* launches only: the CEP_K_CF_PARTITION launches that ran k_cfpart2 */
+  CEP_K_JOIN = 13,                            /* windowed stream joins: every kernel of join_kernels.hip */
+  CEP_K_JOIN_VM = 14                          /* launches only: the join probe passes whose `on` ran on the interpreter */
 };
 
 /* ---- plan-level calls (no device needed) ------------------------------ */
