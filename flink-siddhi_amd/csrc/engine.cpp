@@ -218,6 +218,25 @@ struct JoinRT {
   HostBuf total;               // pinned: the chunk's row total (read back before the emit pass)
 };
 
+// Event table (tab_kernels.hip): one pipeline per table holding every
+// operation on it.  The generic partition pass (N-state record form: one
+// "state" per operation) and k_tabwalk, chunk by chunk, double buffered like a
+// pattern's arenas.  State: a present bit and the row's words per key.
+struct TableRT {
+  int tab = -1;                // index into CompiledApp::tables
+  int run_at = -1;             // query index at which the pipeline runs (its first reader, else its first operation)
+  PatternArgs pa{};            // k_partition's view of the operations
+  TabArgs ta{};                // the plan's part of the walk's arguments
+  bool vm = false;             // k_tabwalk needs the interpreter
+  DevBuf thdr, tword;
+  int64_t kstride = 0;
+  DevBuf recs[2], tile_off[2], chunk_base[2];
+  hipEvent_t part_done[2] = {nullptr, nullptr}, walk_done[2] = {nullptr, nullptr};
+  bool used[2] = {false, false};
+  int cur = 0;
+  int64_t chunk = 0;
+};
+
 struct TimedLaunch {
   int kind;
   hipEvent_t a, b;
@@ -247,6 +266,8 @@ struct cep_app {
   std::vector<PatternRT> pats;
   std::vector<MqRT> mqs;          // multi-query groups
   std::vector<JoinRT> joins;      // windowed stream joins
+  std::vector<TableRT> tabs;      // event tables
+  DevBuf tab_dropped;             // inserts dropped on an existing key (device counter, every table)
   std::vector<char> in_mq;        // per query: served by a multi-query group
   DevBuf tile_state, ticket, err;
   DevBuf route_arena, route_tcount, route_toffs, route_dcount;   // key shuffle (sender)
@@ -287,6 +308,7 @@ struct cep_app {
     DevBuf keys, idx_in, idx_out, temp, bound;
   } ro;
   int64_t events_in = 0, matches_out = 0, batches = 0, late_events = 0;
+  int64_t tab_vm_launches = 0;   // k_tabwalk launches of the interpreter build
   int64_t last_ts = INT64_MIN;
   DevBuf last_ts_dev;          // last ts of the previous batch (RowsArgs::prev_ts_dev)
   bool force_tolerant = false; // this batch holds late rows (cep_watermark, late_policy 2)
@@ -1409,6 +1431,98 @@ int create_runtime(cep_app* a) {
     hipMemset(rt.st.p, 0, sizeof(JoinState));
     a->joins.push_back(rt);
   }
+  // event tables: per table one pipeline over all its operations
+  if (!app.tables.empty()) {
+    if (a->opt.sparse_keys)
+      return fail(a, CEP_E_UNSUPPORTED, "sparse_keys is not supported for an app that holds a table: a table's keys "
+                                        "are its primary-key values themselves (dense, no key map)");
+    if (!dev_ensure(&a->tab_dropped, 64, a->stream, false)) return fail(a, CEP_E_DEVICE, "out of device memory");
+    hipMemset(a->tab_dropped.p, 0, 64);
+  }
+  for (size_t ti = 0; ti < app.tables.size(); ++ti) {
+    const TableDef& T = app.tables[ti];
+    if (T.ops.empty()) continue;   // nobody reads or writes it
+    TableRT rt;
+    rt.tab = (int)ti;
+    PatternArgs& p = rt.pa;
+    p.a_stream = T.a_stream;
+    p.b_stream = -1;
+    p.f_prog = p.g_raw_prog = p.g_walk_prog = -1;
+    p.within = -1;
+    p.having_prog = -1;
+    p.nrec_a = (int)T.rec_a.size();
+    p.nrec_b = (int)T.rec_b.size();
+    for (int i = 0; i < p.nrec_a; ++i) p.rec_a[i] = T.rec_a[i];
+    for (int i = 0; i < p.nrec_b; ++i) p.rec_b[i] = T.rec_b[i];
+    p.rec_words = 2 + std::max(p.nrec_a, p.nrec_b);
+    p.key_capacity = a->opt.key_capacity;
+    p.key_stride = std::max(1, a->opt.key_stride);
+    p.key_offset = a->opt.key_offset;
+    int lg = std::max(0, std::min(12, a->opt.buckets_log2));
+    while ((p.key_capacity >> lg) > kWalkMaxKeys && lg < 12) ++lg;
+    if ((p.key_capacity + (1 << lg) - 1) >> lg > kWalkMaxKeys)
+      return fail(a, CEP_E_CAPACITY, "key_capacity exceeds 1024 * 4096 keys");
+    p.buckets_log2 = lg;
+    const int64_t kpb = (p.key_capacity + (1 << lg) - 1) >> lg;
+    rt.kstride = kpb << lg;
+    // operation j stands where state j of an N-state pattern stands
+    p.nfa_mode = 1;
+    p.nstates = (int)T.ops.size();
+    for (int i = 0; i < 8; ++i) p.key_col_s[i] = T.key_col_s[i];
+    p.key_col_a = p.key_col_b = T.key_col_s[T.a_stream];
+    TabArgs& ta = rt.ta;
+    ta.nops = p.nstates;
+    ta.nwords = (int)T.schema.attrs.size();
+    for (int j = 0; j < p.nstates; ++j) {
+      const Query& q = app.queries[T.ops[j]];
+      p.st_stream[j] = q.in_stream;
+      p.st_min[j] = p.st_max[j] = 1;
+      p.st_raw[j] = q.filter.off;
+      p.st_walk[j] = -1;
+      p.stream_mask |= 1 << q.in_stream;
+      TabOp& op = ta.op[j];
+      op.kind = q.tab_op;
+      op.negate = q.tab_negate ? 1 : 0;
+      op.on_prog = q.tab_on.off;
+      op.reader = (q.tab_op == TOP_JOIN || q.tab_op == TOP_IN) ? 1 : 0;
+      for (int w = 0; w < kMaxCaps; ++w) {
+        op.ins[w] = q.tab_ins[w];
+        op.set[w] = q.tab_set[w];
+      }
+      if (op.reader) {
+        ++ta.nreaders;
+        if (rt.run_at < 0) rt.run_at = T.ops[j];
+        rt.vm |= q.tab_on.valid();
+        for (auto& it : q.select) rt.vm |= it.src == SRC_VM;
+      }
+    }
+    if (rt.run_at < 0) rt.run_at = T.ops[0];
+    // the rows are the one state here that grows with a plan constant
+    const double bytes = (double)rt.kstride * (4 + 8.0 * ta.nwords);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > (double)free_b)
+      return fail(a, CEP_E_CAPACITY, "table " + T.schema.id + ": state of " + std::to_string((unsigned long long)bytes) +
+                                         " bytes (" + std::to_string(rt.kstride) + " keys x " +
+                                         std::to_string(ta.nwords) + " words) exceeds the GPU's free memory: lower "
+                                         "key_capacity");
+    int64_t chunk = std::max<int64_t>(a->opt.chunk_events, kPartThreads * kPartItems);
+    chunk = std::min<int64_t>(chunk, (int64_t)kWalkMaxTiles * kPartThreads * kPartItems);
+    chunk = (chunk / (kPartThreads * kPartItems)) * (kPartThreads * kPartItems);
+    rt.chunk = chunk;
+    const int64_t ntiles = chunk / (kPartThreads * kPartItems);
+    bool ok = dev_ensure(&rt.thdr, (size_t)rt.kstride * 4, a->stream, false) &&
+              dev_ensure(&rt.tword, (size_t)rt.kstride * ta.nwords * 8, a->stream, false);
+    for (int b = 0; b < 2 && ok; ++b)
+      ok = dev_ensure(&rt.recs[b], (size_t)chunk * p.rec_words * 8 + 16, a->stream, false) &&
+           dev_ensure(&rt.tile_off[b], (size_t)ntiles * ((1 << lg) + 1) * 2, a->stream, false) &&
+           dev_ensure(&rt.chunk_base[b], 64, a->stream, false) &&
+           hipEventCreateWithFlags(&rt.part_done[b], hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(&rt.walk_done[b], hipEventDisableTiming) == hipSuccess;
+    if (!ok) return fail(a, CEP_E_DEVICE, "out of device memory (table " + T.schema.id + ")");
+    hipMemset(rt.thdr.p, 0, (size_t)rt.kstride * 4);
+    hipMemset(rt.tword.p, 0, (size_t)rt.kstride * ta.nwords * 8);
+    a->tabs.push_back(rt);
+  }
   {
     const int64_t none = INT64_MIN;
     if (!dev_ensure(&a->last_ts_dev, 64, a->stream, false) ||
@@ -1427,6 +1541,8 @@ const StreamSchema* find_schema(cep_app* a, const char* id) {
   if (i >= 0) return &a->app.inputs[i];
   i = a->app.output_index(id);
   if (i >= 0) return &a->app.outputs[i];
+  i = a->app.table_index(id);   // (cep_stream_schema also describes a table)
+  if (i >= 0) return &a->app.tables[i].schema;
   return nullptr;
 }
 
@@ -2401,6 +2517,83 @@ int run_join(cep_app* a, JoinRT& rt, const RowsArgs& rows_in) {
   return CEP_OK;
 }
 
+// One table's operations over a device batch, chunk by chunk: k_partition (its
+// N-state record form) on the side stream, k_tabwalk on the main stream,
+// double-buffered arenas as in run_pattern.  A reader emits at most one row
+// per row of its stream: the outputs are sized before the launch.
+int run_table(cep_app* a, TableRT& rt, const RowsArgs& rows_all) {
+  const TableDef& T = a->app.tables[rt.tab];
+  if (!rows_all.stream && !((rt.pa.stream_mask >> rows_all.input) & 1)) return CEP_OK;   // no operation reads it
+  if (rows_all.seq)
+    return fail(a, CEP_E_UNSUPPORTED, "row shuffle of an app that holds a table is not supported");
+  for (int j = 0; j < rt.ta.nops; ++j) {
+    if (!rt.ta.op[j].reader) continue;
+    const Query& q = a->app.queries[T.ops[j]];
+    OutStream& o = a->outs[a->app.output_index(q.out_stream)];
+    o.bound += rows_all.n;
+    const int rc = ensure_out_cap(a, o, o.bound);
+    if (rc) return rc;
+  }
+  const int P = 1 << rt.pa.buckets_log2;
+  hipEventRecord(a->in_ready, a->stream);
+  hipStreamWaitEvent(a->side, a->in_ready, 0);
+  static const bool no_overlap = std::getenv("CEP_NO_OVERLAP") != nullptr;
+  hipStream_t side = no_overlap ? a->stream : a->side;
+  for (int64_t r0 = 0; r0 < rows_all.n; r0 += rt.chunk) {
+    const int b = rt.cur;
+    rt.cur ^= 1;
+    RowsArgs rows = rows_all;
+    rows.row0 = rows_all.row0 + r0;
+    rows.n = std::min<int64_t>(rt.chunk, rows_all.n - r0);
+    rows.prev_ts = INT64_MIN;   // timestamps play no part: no order check
+    rows.prev_ts_dev = nullptr;
+    const int64_t ntiles = (rows.n + kPartThreads * kPartItems - 1) / (kPartThreads * kPartItems);
+    PartArgs pa{};
+    pa.rows = rows;
+    pa.pref.n = -1;
+    pa.vm = {(const Ins*)a->code.p, (const uint64_t*)a->konst.p};
+    pa.pat = rt.pa;
+    pa.tile_rows = kPartThreads * kPartItems;
+    pa.recs = (uint64_t*)rt.recs[b].p;
+    pa.tile_off = (uint16_t*)rt.tile_off[b].p;
+    pa.chunk_base = (int64_t*)rt.chunk_base[b].p;
+    pa.err = (unsigned int*)a->err.p;
+    if (rt.used[b]) hipStreamWaitEvent(side, rt.walk_done[b], 0);   // arena b is free
+    {
+      LaunchTimer t(a, CEP_K_PARTITION, side);
+      launch_partition(pa, ntiles, true, side);   // (the N-state record form is the interpreter build's)
+    }
+    hipEventRecord(rt.part_done[b], side);
+    hipStreamWaitEvent(a->stream, rt.part_done[b], 0);
+    TabArgs ta = rt.ta;
+    ta.vm = pa.vm;
+    ta.pat = pa.pat;
+    ta.recs = pa.recs;
+    ta.tile_off = pa.tile_off;
+    ta.ntiles = (int)ntiles;
+    ta.tile_rows = pa.tile_rows;
+    ta.chunk_base = pa.chunk_base;
+    ta.thdr = (uint32_t*)rt.thdr.p;
+    ta.tword = (uint64_t*)rt.tword.p;
+    ta.kstride = rt.kstride;
+    for (int j = 0; j < ta.nops; ++j) {
+      if (!ta.op[j].reader) continue;
+      const Query& q = a->app.queries[T.ops[j]];
+      ta.out[j] = out_args(a->outs[a->app.output_index(q.out_stream)], q);
+    }
+    ta.dropped = (unsigned long long*)a->tab_dropped.p;
+    ta.err = pa.err;
+    {
+      LaunchTimer t(a, CEP_K_TABLE);
+      if (rt.vm) a->tab_vm_launches++;
+      launch_tabwalk(ta, P, rt.vm, a->stream);
+    }
+    hipEventRecord(rt.walk_done[b], a->stream);
+    rt.used[b] = true;
+  }
+  return CEP_OK;
+}
+
 int send_device_rows(cep_app* a, const RowsArgs& rows_in) {
   // query chaining: each view is built once per slice, before its first reader
   std::vector<RowsArgs> views(a->app.views.size());
@@ -2437,6 +2630,10 @@ int send_device_rows(cep_app* a, const RowsArgs& rows_in) {
     } else if (q.kind == Q_JOIN) {
       for (auto& rt : a->joins)
         if (rt.q == (int)qi) rc = run_join(a, rt, rows);
+    } else if (q.kind == Q_TABLE) {
+      // every operation of the table runs in one pipeline, at its first reader
+      for (auto& rt : a->tabs)
+        if (rt.run_at == (int)qi) rc = run_table(a, rt, rows);
     }
     if (rc) return rc;
   }
@@ -2784,6 +2981,16 @@ void cep_destroy(cep_app* a) {
       dev_free(b);
     host_free(&jr.total);
   }
+  for (auto& tr : a->tabs) {
+    for (DevBuf* b : {&tr.thdr, &tr.tword, &tr.recs[0], &tr.recs[1], &tr.tile_off[0], &tr.tile_off[1],
+                      &tr.chunk_base[0], &tr.chunk_base[1]})
+      dev_free(b);
+    for (int b = 0; b < 2; ++b) {
+      if (tr.part_done[b]) hipEventDestroy(tr.part_done[b]);
+      if (tr.walk_done[b]) hipEventDestroy(tr.walk_done[b]);
+    }
+  }
+  dev_free(&a->tab_dropped);
   if (a->copy) hipStreamSynchronize(a->copy);
   for (auto& h : a->hs) {
     host_free(&h.pinned);
@@ -3356,6 +3563,12 @@ int cep_stats(cep_app* a, cep_stats_t* s) {
   s->late_events = a->late_events;
   for (auto& p : a->pats)
     if (p.hot) s->hot_keys += *(volatile uint32_t*)p.hot_active_host.p;
+  s->table_vm_launches = a->tab_vm_launches;
+  if (a->tab_dropped.p) {
+    unsigned long long d = 0;
+    hipMemcpy(&d, a->tab_dropped.p, 8, hipMemcpyDeviceToHost);
+    s->table_dropped = (int64_t)d;
+  }
   for (int i = 0; i < 16; ++i) {
     s->kernel_launches[i] = a->launches[i];
     s->kernel_ms[i] = a->kernel_ms[i];
@@ -3411,6 +3624,24 @@ static uint64_t plan_hash(const CompiledApp& app) {
     mix(w, sizeof(w));
     for (int c : q.rec_cols_a) mix(&c, sizeof(c));
   }
+  // tables: definitions and operations (plans without a table hash as before)
+  for (size_t ti = 0; ti < app.tables.size(); ++ti) {
+    const TableDef& T = app.tables[ti];
+    const int64_t w[4] = {-4, (int64_t)ti, T.pk, (int64_t)T.schema.attrs.size()};
+    mix(w, sizeof(w));
+    mix(T.schema.id.data(), T.schema.id.size());
+    for (auto& at : T.schema.attrs) {
+      mix(at.name.data(), at.name.size());
+      mix(&at.type, sizeof(at.type));
+    }
+    for (int qi : T.ops) {
+      const Query& q = app.queries[qi];
+      const int64_t o[6] = {-5, qi, q.tab_op, q.in_stream, q.tab_key_col, q.tab_negate ? 1 : 0};
+      mix(o, sizeof(o));
+      mix(q.tab_ins, sizeof(q.tab_ins));
+      mix(q.tab_set, sizeof(q.tab_set));
+    }
+  }
   // query chaining (plans without derived streams hash as before)
   for (auto& d : app.derived) {
     const int64_t w[5] = {-1, d.stream, d.producer, d.source, d.stage};
@@ -3436,7 +3667,7 @@ int cep_snapshot(cep_app* a, uint8_t** buf, size_t* len) {
   const char magic[4] = {'C', 'E', 'P', 'S'};
   put(magic, 4);
   // 3: + the event-time reorder buffer; 4: + pending counts (overflow runs); 5: + groups; 6: + joins
-  uint32_t ver = a->joins.empty() ? 5 : 6;
+  uint32_t ver = !a->tabs.empty() ? 7 : a->joins.empty() ? 5 : 6;
   put(&ver, 4);
   uint64_t h = plan_hash(a->app);
   put(&h, 8);
@@ -3546,7 +3777,7 @@ int cep_snapshot(cep_app* a, uint8_t** buf, size_t* len) {
     }
   }
   // (version 6) joins: each side's live rows (the list's tail) and counts
-  if (!a->joins.empty()) {
+  if (ver >= 6) {
     const uint32_t nj = (uint32_t)a->joins.size();
     put(&nj, 4);
     for (auto& jr : a->joins) {
@@ -3563,6 +3794,35 @@ int cep_snapshot(cep_app* a, uint8_t** buf, size_t* len) {
         put(rows.data(), rows.size() * 8);
       }
     }
+  }
+  // (version 7) tables: per table its live rows, by dense key
+  if (ver >= 7) {
+    const uint32_t nt = (uint32_t)a->tabs.size();
+    put(&nt, 4);
+    for (auto& tr : a->tabs) {
+      const int64_t ks = tr.kstride, kc = tr.pa.key_capacity;
+      const int lg = tr.pa.buckets_log2;
+      const int64_t kpb = ks >> lg;
+      const uint32_t nw = (uint32_t)tr.ta.nwords;
+      std::vector<uint32_t> hdr(ks);
+      std::vector<uint64_t> words((size_t)ks * nw);
+      hipMemcpy(hdr.data(), tr.thdr.p, hdr.size() * 4, hipMemcpyDeviceToHost);
+      hipMemcpy(words.data(), tr.tword.p, words.size() * 8, hipMemcpyDeviceToHost);
+      uint32_t live = 0;
+      for (int64_t i = 0; i < ks; ++i) live += hdr[i] & 1u;
+      put(&kc, 8);
+      put(&nw, 4);
+      put(&live, 4);
+      for (int64_t i = 0; i < ks; ++i) {
+        if (!(hdr[i] & 1u)) continue;
+        const uint32_t key = (uint32_t)(((i % kpb) << lg) | (i / kpb));   // dense key
+        put(&key, 4);
+        for (uint32_t w = 0; w < nw; ++w) put(&words[(size_t)w * ks + i], 8);
+      }
+    }
+    unsigned long long d = 0;
+    hipMemcpy(&d, a->tab_dropped.p, 8, hipMemcpyDeviceToHost);
+    put(&d, 8);
   }
   *buf = (uint8_t*)std::malloc(out.size());
   if (!*buf) return fail(a, CEP_E_DEVICE, "out of host memory");
@@ -3585,7 +3845,7 @@ int cep_restore(cep_app* a, const uint8_t* buf, size_t len) {
   uint64_t h;
   int64_t ev;
   uint32_t np;
-  if (!get(magic, 4) || std::memcmp(magic, "CEPS", 4) || !get(&ver, 4) || ver < 2 || ver > 6 || !get(&h, 8) ||
+  if (!get(magic, 4) || std::memcmp(magic, "CEPS", 4) || !get(&ver, 4) || ver < 2 || ver > 7 || !get(&h, 8) ||
       !get(&ev, 8) || !get(&np, 4))
     return fail(a, CEP_E_STATE, "not a libcep snapshot");
   if (h != plan_hash(a->app) || np != a->pats.size())
@@ -3761,6 +4021,42 @@ int cep_restore(cep_app* a, const uint8_t* buf, size_t len) {
   } else if (!a->joins.empty()) {
     return fail(a, CEP_E_STATE, "snapshot has no join state (version < 6)");
   }
+  // (version 7) tables
+  struct TabSnap {
+    std::vector<uint32_t> hdr;
+    std::vector<uint64_t> words;
+  };
+  std::vector<TabSnap> tsn(a->tabs.size());
+  unsigned long long tab_dropped = 0;
+  if (ver >= 7) {
+    uint32_t nt;
+    if (!get(&nt, 4) || nt != a->tabs.size()) return fail(a, CEP_E_STATE, "snapshot tables do not match");
+    for (size_t ti = 0; ti < a->tabs.size(); ++ti) {
+      const TableRT& tr = a->tabs[ti];
+      int64_t kc;
+      uint32_t nw, live;
+      if (!get(&kc, 8) || !get(&nw, 4) || !get(&live, 4)) return fail(a, CEP_E_STATE, "truncated snapshot");
+      if (kc != tr.pa.key_capacity || nw != (uint32_t)tr.ta.nwords || (uint64_t)live > (uint64_t)kc)
+        return fail(a, CEP_E_STATE, "snapshot geometry differs from this runtime (table rows)");
+      if ((uint64_t)live * (4 + 8ull * nw) > len - off) return fail(a, CEP_E_STATE, "truncated snapshot");
+      const int64_t ks = tr.kstride;
+      const int lg = tr.pa.buckets_log2;
+      const int64_t kpb = ks >> lg;
+      tsn[ti].hdr.assign(ks, 0);
+      tsn[ti].words.assign((size_t)ks * nw, 0);
+      for (uint32_t i = 0; i < live; ++i) {
+        uint32_t key;
+        get(&key, 4);
+        if (key >= kc) return fail(a, CEP_E_STATE, "corrupt snapshot");
+        const int64_t idx = (int64_t)(key & ((1u << lg) - 1)) * kpb + (key >> lg);
+        tsn[ti].hdr[idx] = 1;
+        for (uint32_t w = 0; w < nw; ++w) get(&tsn[ti].words[(size_t)w * ks + idx], 8);
+      }
+    }
+    if (!get(&tab_dropped, 8)) return fail(a, CEP_E_STATE, "truncated snapshot");
+  } else if (!a->tabs.empty()) {
+    return fail(a, CEP_E_STATE, "snapshot has no table state (version < 7)");
+  }
   // Phase 2: commit (device allocations first, so a failure leaves the
   // runtime as it was)
   auto& r = a->ro;
@@ -3828,11 +4124,77 @@ int cep_restore(cep_app* a, const uint8_t* buf, size_t len) {
     }
     hipMemcpy(jr.st.p, &st, sizeof(st), hipMemcpyHostToDevice);
   }
+  for (size_t ti = 0; ti < a->tabs.size(); ++ti) {
+    TableRT& tr = a->tabs[ti];
+    hipMemcpy(tr.thdr.p, tsn[ti].hdr.data(), tsn[ti].hdr.size() * 4, hipMemcpyHostToDevice);
+    hipMemcpy(tr.tword.p, tsn[ti].words.data(), tsn[ti].words.size() * 8, hipMemcpyHostToDevice);
+  }
+  if (a->tab_dropped.p) hipMemcpy(a->tab_dropped.p, &tab_dropped, 8, hipMemcpyHostToDevice);
   a->events_in = ev;
   return CEP_OK;
 }
 
+static const char* kTableShuffle = "the key / row shuffle of an app that holds a table is not supported";
+
+// The live rows of table `table_id`, ordered by primary key, columns = the
+// table's attributes (ts / seq NULL).  On a shard: the keys it owns.
+int cep_table_rows(cep_app* a, const char* table_id, cep_emit_fn fn, void* user) {
+  if (!a || !table_id || !fn) return CEP_E_ARG;
+  const int ti = a->app.table_index(table_id);
+  if (ti < 0) return fail(a, CEP_E_UNDEFINED_STREAM, std::string("Table ") + table_id + " not defined");
+  if (hipStreamSynchronize(a->stream) != hipSuccess) return fail(a, CEP_E_DEVICE, "device failure");
+  harvest_timers(a);
+  const TableDef& T = a->app.tables[ti];
+  const TableRT* tr = nullptr;
+  for (auto& t : a->tabs)
+    if (t.tab == ti) tr = &t;
+  const size_t nc = T.schema.attrs.size();
+  std::vector<std::vector<uint8_t>> cols(nc);
+  int64_t n = 0;
+  if (tr) {
+    const int64_t ks = tr->kstride, kc = tr->pa.key_capacity;
+    const int lg = tr->pa.buckets_log2;
+    const int64_t kpb = ks >> lg;
+    std::vector<uint32_t> hdr(ks);
+    std::vector<uint64_t> words((size_t)ks * nc);
+    if (hipMemcpy(hdr.data(), tr->thdr.p, hdr.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(words.data(), tr->tword.p, words.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
+      return fail(a, CEP_E_DEVICE, "device failure (table rows)");
+    // dense keys ascending = primary keys ascending (key = dense * stride + offset)
+    for (int64_t key = 0; key < kc; ++key) {
+      const int64_t idx = (key & ((1 << lg) - 1)) * kpb + (key >> lg);
+      if (!(hdr[idx] & 1u)) continue;
+      for (size_t c = 0; c < nc; ++c) {
+        const uint64_t v = words[c * (size_t)ks + idx];
+        const int w = type_width(T.schema.attrs[c].type);
+        uint8_t bytes[8];
+        if (w == 1) bytes[0] = (uint8_t)(v & 1u);
+        else if (w == 4) { const uint32_t x = (uint32_t)v; std::memcpy(bytes, &x, 4); }
+        else std::memcpy(bytes, &v, 8);
+        cols[c].insert(cols[c].end(), bytes, bytes + w);
+      }
+      ++n;
+    }
+  }
+  if (n == 0) return CEP_OK;
+  std::vector<const void*> ptrs(nc);
+  for (size_t c = 0; c < nc; ++c) ptrs[c] = cols[c].data();
+  cep_rows rows{};
+  rows.stream_id = T.schema.id.c_str();
+  rows.n = n;
+  rows.ncols = (int32_t)nc;
+  rows.ts = nullptr;
+  rows.seq = nullptr;
+  rows.cols = ptrs.data();
+  fn(user, &rows);
+  return CEP_OK;
+}
+
 int cep_record_words(cep_app* a) {
+  if (a && !a->app.tables.empty()) {
+    fail(a, CEP_E_UNSUPPORTED, kTableShuffle);
+    return -CEP_E_UNSUPPORTED;
+  }
   if (a && !a->joins.empty()) {
     fail(a, CEP_E_UNSUPPORTED, "key shuffle of an app that holds a join is not supported: its windows are global, "
                                "not per key");
@@ -3858,6 +4220,7 @@ static int route_batch(cep_app* a, const cep_batch* b, int world, int64_t seq0, 
   if (!a->app.derived.empty())
     return fail(a, CEP_E_UNSUPPORTED, "key shuffle of an app with query chaining (derived streams) is not supported: "
                                       "the sender needs the key in source columns");
+  if (!a->app.tables.empty()) return fail(a, CEP_E_UNSUPPORTED, kTableShuffle);
   if (!a->joins.empty())
     return fail(a, CEP_E_UNSUPPORTED, "key shuffle of an app that holds a join is not supported: its windows are "
                                       "global, not per key");
@@ -4015,6 +4378,7 @@ static int row_route_plan(cep_app* a, int32_t (&kc)[8], int* layout) {
   const CompiledApp& app = a->app;
   const int ni = (int)app.inputs.size();
   if (ni > 8) return fail(a, CEP_E_UNSUPPORTED, "row shuffle supports at most 8 input streams");
+  if (!app.tables.empty()) return fail(a, CEP_E_UNSUPPORTED, kTableShuffle);
   if (!a->joins.empty())
     return fail(a, CEP_E_UNSUPPORTED, "row shuffle of an app that holds a join is not supported: its windows are "
                                       "global, not per key");

@@ -14,6 +14,14 @@
 //               | state ('->' state)* ['within' time]          (patterns)
 //   state      := ['every'] ID '=' ID ['[' expr ']']
 //   partition  := 'partition' 'with' '(' ID 'of' ID {',' ...} ')' 'begin' {query ';'} 'end'
+// Event tables:
+//   define     := '@PrimaryKey' '(' STR ')' 'define' 'table' ID '(' ID type {',' ID type} ')'
+//   query      := 'from' ID {'[' expr ']'} 'select' ... writer
+//   writer     := 'insert' 'into' T | 'update' 'or' 'insert' 'into' T [set] 'on' expr
+//               | 'update' T [set] 'on' expr | 'delete' T 'on' expr
+//   set        := 'set' T '.' ID '=' ID {',' T '.' ID '=' ID}
+//   input      := side ['inner'] 'join' side 'on' expr   (one side a table: lookup join)
+//   expr       := ... | expr 'in' T                      (`(T.k == x) in T`, filter conjunct)
 // Expressions: or/and/not, == != < <= > >=, + - * / %, unary -, literals
 // (int, long L, float f, double, 'string', true/false), attribute refs
 // (x, s.x, s[0].x, s[last].x), aggregates sum/count/avg/min/max.
@@ -167,7 +175,7 @@ std::vector<Token> tokenize(const std::string& s) {
 struct Expr;
 using ExprP = std::shared_ptr<Expr>;
 struct Expr {
-  enum K { CONST, ATTR, BIN, NOT, NEG, CALL } k;
+  enum K { CONST, ATTR, BIN, NOT, NEG, CALL, IN } k;   // IN: args[0] `in` table `name`
   std::string op;            // BIN operator / CALL name
   std::vector<ExprP> args;
   int vtype = -1;            // CONST type
@@ -218,8 +226,20 @@ struct QueryAst {
   std::vector<ExprP> group_by;
   ExprP having;
   std::string out;
+  // output clause: `insert into` a stream or table, or a table writer
+  enum OutKind { OUT_INSERT, OUT_UPSERT, OUT_UPDATE, OUT_DELETE } out_kind = OUT_INSERT;
+  std::vector<std::pair<ExprP, ExprP>> out_set;   // `set T.x = y`
+  ExprP out_on;                                   // `on T.k == y`
   bool partitioned = false;
   std::map<std::string, std::string> partition;  // stream -> key attr
+};
+
+// `define table` with the annotations in front of it.
+struct TableAst {
+  StreamSchema schema;
+  std::vector<std::string> pk;     // @PrimaryKey arguments
+  bool has_pk = false;
+  std::string other;               // @Index / @Store, when present
 };
 
 int64_t time_unit_ms(const std::string& u) {
@@ -238,17 +258,26 @@ int64_t time_unit_ms(const std::string& u) {
 
 class Parser {
  public:
-  explicit Parser(const std::string& text) : toks_(tokenize(text)) {}
+  explicit Parser(const std::string& text) : toks_(tokenize(text)) {
+    // table ids, known before the first query is parsed (a join form that is
+    // refused by name says so differently when a side is a table)
+    for (size_t i = 0; i + 2 < toks_.size(); ++i)
+      if (toks_[i].k == TK_KW && toks_[i].v == "define" && toks_[i + 1].k == TK_KW && toks_[i + 1].v == "table" &&
+          toks_[i + 2].k == TK_ID)
+        table_ids_.insert(toks_[i + 2].v);
+  }
 
-  void parse(std::vector<StreamSchema>* streams, std::vector<QueryAst>* qs) {
+  void parse(std::vector<StreamSchema>* streams, std::vector<QueryAst>* qs, std::vector<TableAst>* tables) {
     while (peek().k != TK_EOF) {
       if (accept(TK_OP, ";")) continue;
-      while (peek().k == TK_OP && peek().v == "@") skip_annotation();
+      TableAst ta;   // annotations that matter to a table definition
+      while (peek().k == TK_OP && peek().v == "@") annotation(&ta);
       const Token& t = peek();
       if (t.k == TK_KW && t.v == "define") {
         next();
-        if (!(peek().k == TK_KW && peek().v == "stream"))
-          fail(CEP_E_UNSUPPORTED, "only 'define stream' is supported (got define " +
+        const bool table = peek().k == TK_KW && peek().v == "table";
+        if (!table && !(peek().k == TK_KW && peek().v == "stream"))
+          fail(CEP_E_UNSUPPORTED, "only 'define stream' and 'define table' are supported (got define " +
                                       peek().v + ")");
         next();
         StreamSchema sd;
@@ -277,7 +306,15 @@ class Parser {
         for (auto& s : *streams)
           if (s.id == sd.id)
             fail(CEP_E_DUPLICATED_STREAM, "stream " + sd.id + " already defined");
-        streams->push_back(sd);
+        for (auto& tb : *tables)
+          if (tb.schema.id == sd.id)
+            fail(CEP_E_DUPLICATED_STREAM, "table " + sd.id + " already defined");
+        if (table) {
+          ta.schema = sd;
+          tables->push_back(ta);
+        } else {
+          streams->push_back(sd);
+        }
       } else if (t.k == TK_KW && t.v == "from") {
         qs->push_back(query());
       } else if (t.k == TK_KW && t.v == "partition") {
@@ -295,6 +332,7 @@ class Parser {
  private:
   std::vector<Token> toks_;
   size_t i_ = 0;
+  std::set<std::string> table_ids_;
 
   const Token& peek(size_t k = 0) const {
     return toks_[std::min(i_ + k, toks_.size() - 1)];
@@ -321,10 +359,14 @@ class Parser {
     ++i_;
     return t.v;
   }
-  void skip_annotation() {
+  // Annotations are skipped, except the ones a table definition depends on:
+  // @PrimaryKey's arguments, and the presence of @Index / @Store.
+  void annotation(TableAst* ta) {
     expect(TK_OP, "@");
-    next();
+    const std::string name = lower(next().v);
     if (accept(TK_OP, ":")) next();
+    if (name == "primarykey") ta->has_pk = true;
+    if (name == "index" || name == "store") ta->other = name;
     if (accept(TK_OP, "(")) {
       int depth = 1;
       while (depth) {
@@ -332,8 +374,18 @@ class Parser {
         if (t.k == TK_EOF) fail(CEP_E_PARSE, "unterminated annotation");
         if (t.k == TK_OP && t.v == "(") ++depth;
         if (t.k == TK_OP && t.v == ")") --depth;
+        if (name == "primarykey" && depth == 1 && (t.k == TK_STR || t.k == TK_ID)) ta->pk.push_back(t.v);
       }
     }
+  }
+
+  // Whether the join being parsed has a table side: `first`, or the
+  // identifier after the coming `join`.
+  bool table_join(const std::string& first) const {
+    if (table_ids_.count(first)) return true;
+    for (size_t k = 0; k < 4; ++k)
+      if (peek(k).k == TK_KW && peek(k).v == "join") return peek(k + 1).k == TK_ID && table_ids_.count(peek(k + 1).v);
+    return false;
   }
 
   void partition(std::vector<QueryAst>* qs) {
@@ -379,9 +431,13 @@ class Parser {
       // every other join form is refused here by name
       auto word = [&](const char* w) { return peek().k == TK_ID && lower(peek().v) == w; };
       if (peek().k == TK_KW && peek().v == "unidirectional")
-        fail(CEP_E_UNSUPPORTED, "unidirectional joins are not supported");
+        fail(CEP_E_UNSUPPORTED, table_join(q.stream) ? "a unidirectional join against a table is not supported"
+                                                     : "unidirectional joins are not supported");
       if (word("left") || word("right") || word("full") || word("outer"))
-        fail(CEP_E_UNSUPPORTED, "outer joins (" + lower(peek().v) + " ... join) are not supported, only the inner join");
+        fail(CEP_E_UNSUPPORTED, table_join(q.stream)
+                                    ? "outer joins (" + lower(peek().v) + " ... join) against a table are not supported, "
+                                      "only the inner join"
+                                    : "outer joins (" + lower(peek().v) + " ... join) are not supported, only the inner join");
       if (word("inner") && peek(1).k == TK_KW && peek(1).v == "join") next();
       if (accept(TK_KW, "join")) {
         q.join = true;
@@ -389,7 +445,9 @@ class Parser {
           fail(CEP_E_UNSUPPORTED, "inner streams (join #" + peek(1).v + ") are not supported");
         side(&q.stream2, &q.alias2, &q.filters2, &q.win_kind2, &q.win_param2);
         if (peek().k == TK_KW && peek().v == "unidirectional")
-          fail(CEP_E_UNSUPPORTED, "unidirectional joins are not supported");
+          fail(CEP_E_UNSUPPORTED, (table_ids_.count(q.stream) || table_ids_.count(q.stream2))
+                                      ? "a unidirectional join against a table is not supported"
+                                      : "unidirectional joins are not supported");
         if (accept(TK_KW, "on")) q.on = expr();
         if (peek().k == TK_KW && peek().v == "within")
           fail(CEP_E_UNSUPPORTED, "`within` on a join is not supported");
@@ -436,6 +494,33 @@ class Parser {
       }
     }
     if (accept(TK_KW, "having")) q.having = expr();
+    // table writers: `update or insert into T`, `update T`, `delete T`
+    auto idword = [&](const char* w) { return peek().k == TK_ID && lower(peek().v) == w; };
+    if (idword("update") || idword("delete")) {
+      const bool del = idword("delete");
+      next();
+      if (!del && accept(TK_KW, "or")) {
+        expect(TK_KW, "insert");
+        expect(TK_KW, "into");
+        q.out_kind = QueryAst::OUT_UPSERT;
+      } else {
+        q.out_kind = del ? QueryAst::OUT_DELETE : QueryAst::OUT_UPDATE;
+      }
+      q.out = ident();
+      if (idword("for")) fail(CEP_E_UNSUPPORTED, "`for <x> events` on a table writer is not supported");
+      if (!del && idword("set")) {
+        next();
+        while (true) {
+          ExprP lhs = primary();
+          expect(TK_OP, "=");
+          q.out_set.push_back({lhs, expr()});
+          if (!accept(TK_OP, ",")) break;
+        }
+      }
+      expect(TK_KW, "on");
+      q.out_on = expr();
+      return q;
+    }
     expect(TK_KW, "insert");
     if (peek().k == TK_KW &&
         (peek().v == "all" || peek().v == "current" || peek().v == "expired")) {
@@ -589,6 +674,14 @@ class Parser {
                          t.v == ">" || t.v == ">=")) {
       std::string op = next().v;
       e = bin(op, e, add_expr());
+    }
+    // `<condition> in T` (table membership)
+    while (peek().k == TK_ID && lower(peek().v) == "in" && peek(1).k == TK_ID) {
+      next();
+      auto in = mk(Expr::IN);
+      in->args = {e};
+      in->name = next().v;
+      e = in;
     }
     return e;
   }
@@ -803,6 +896,9 @@ void bind_expr(const ExprP& e, Ctx& c, CompiledApp* app) {
       e->t = c.states[st]->attrs[i].type;
       return;
     }
+    case Expr::IN:
+      fail(CEP_E_UNSUPPORTED, "`in " + e->name + "` (table membership) is supported only as one top-level `and` "
+                              "conjunct of a plain filter query's filter");
     case Expr::NOT:
       bind_expr(e->args[0], c, app);
       if (e->args[0]->t != T_BOOL) fail(CEP_E_PARSE, "'not' requires a bool operand");
@@ -929,6 +1025,8 @@ class CodeGen {
         emit(OP_LDAGG, r, 0, (uint8_t)e->t, (uint32_t)e->agg);
         return;
       }
+      case Expr::IN:
+        fail(CEP_E_UNSUPPORTED, "`in` (table membership) inside an expression is not supported");
       case Expr::NOT:
         gen(e->args[0], r);
         emit(OP_NOT, r, r, 0, 0);
@@ -1844,6 +1942,417 @@ bool same_types(const StreamSchema& x, const StreamSchema& y) {
   return true;
 }
 
+// ------------------------------------------------------ event tables (§11) --
+// A table with a primary key, addressed only by that key, is per-key state:
+// every query that names it becomes one operation (Q_TABLE) of the table's
+// pipeline.  Everything that would need a scan, a second index or a global
+// order is refused with a message that names the table.
+void collect_in(const ExprP& e, std::vector<ExprP>* out) {
+  if (!e) return;
+  if (e->k == Expr::IN) out->push_back(e);
+  for (auto& a : e->args) collect_in(a, out);
+}
+
+void define_tables(CompiledApp* app, const std::vector<TableAst>& tabs) {
+  for (auto& ta : tabs) {
+    const std::string& id = ta.schema.id;
+    const std::string what = "table " + id + ": ";
+    if (app->input_index(id) >= 0) fail(CEP_E_DUPLICATED_STREAM, "table " + id + " is also defined as a stream");
+    if (!ta.other.empty())
+      fail(CEP_E_UNSUPPORTED, what + "@" + ta.other + " is not supported (a table is addressed by its primary key only)");
+    if (!ta.has_pk || ta.pk.empty())
+      fail(CEP_E_UNSUPPORTED, what + "a table without @PrimaryKey is not supported (it would need a scan)");
+    if (ta.pk.size() > 1) fail(CEP_E_UNSUPPORTED, what + "a composite primary key is not supported");
+    TableDef td;
+    td.schema = ta.schema;
+    td.pk = ta.schema.index(ta.pk[0]);
+    if (td.pk < 0) fail(CEP_E_PARSE, what + "primary key " + ta.pk[0] + " is not an attribute of the table");
+    const int kt = ta.schema.attrs[td.pk].type;
+    if (kt != T_INT && kt != T_LONG && kt != T_STRING)
+      fail(CEP_E_UNSUPPORTED, what + "the primary key of a table must be int, long or string");
+    if ((int)ta.schema.attrs.size() > kMaxCaps)
+      fail(CEP_E_UNSUPPORTED, what + "a table of more than " + std::to_string(kMaxCaps) + " attributes is not supported");
+    for (auto& at : ta.schema.attrs)
+      if (at.type == T_OBJECT) fail(CEP_E_UNSUPPORTED, what + "object attributes in a table are not supported");
+    if ((int)app->tables.size() >= kMaxTables)
+      fail(CEP_E_UNSUPPORTED, "more than " + std::to_string(kMaxTables) + " tables in one app are not supported");
+    for (int i = 0; i < 8; ++i) td.key_col_s[i] = -1;
+    app->tables.push_back(td);
+  }
+}
+
+// One operation on a table.  Returns false when the query names no table.
+bool compile_table_query(CompiledApp* app, QueryAst& q) {
+  std::set<std::string> named;
+  const bool writes = q.out_kind != QueryAst::OUT_INSERT || app->table_index(q.out) >= 0;
+  if (q.out_kind != QueryAst::OUT_INSERT && app->table_index(q.out) < 0)
+    fail(CEP_E_UNDEFINED_STREAM, "table " + q.out + " is not defined");
+  if (writes) named.insert(q.out);
+  std::vector<ExprP> ins;
+  for (auto& f : q.filters) collect_in(f, &ins);
+  for (auto& f : q.filters2) collect_in(f, &ins);
+  for (auto& st : q.states) collect_in(st.cond, &ins);
+  collect_in(q.on, &ins);
+  collect_in(q.having, &ins);
+  for (auto& it : q.select) collect_in(it.e, &ins);
+  for (auto& e : ins) {
+    if (app->table_index(e->name) < 0) fail(CEP_E_UNDEFINED_STREAM, "table " + e->name + " is not defined");
+    named.insert(e->name);
+  }
+  bool state_table = false;
+  for (auto& st : q.states)
+    if (app->table_index(st.stream) >= 0) {
+      named.insert(st.stream);
+      state_table = true;
+    }
+  const bool t1 = q.single && app->table_index(q.stream) >= 0;
+  const bool t2 = q.single && q.join && app->table_index(q.stream2) >= 0;
+  if (t1) named.insert(q.stream);
+  if (t2) named.insert(q.stream2);
+  if (named.empty()) return false;
+  const std::string tid = *named.begin();
+  const std::string what = "table " + tid + ": ";
+  if (!q.single)
+    fail(CEP_E_UNSUPPORTED, what + (writes && !state_table ? "a pattern or sequence query that writes a table is not supported"
+                                                           : "a table in a pattern or sequence is not supported"));
+  if (q.partitioned) fail(CEP_E_UNSUPPORTED, what + "a table operation inside `partition with` is not supported");
+  if (t1 && t2) fail(CEP_E_UNSUPPORTED, what + "a join of two tables is not supported");
+  if (named.size() > 1) fail(CEP_E_UNSUPPORTED, what + "two tables in one query are not supported");
+  if (t1 && !q.join)
+    fail(CEP_E_UNSUPPORTED, what + "reading a table as a stream (from " + tid + " ...) is not supported");
+  if (writes && q.join) fail(CEP_E_UNSUPPORTED, what + "a join that writes a table is not supported");
+  if (writes && q.win_kind != WIN_NONE) fail(CEP_E_UNSUPPORTED, what + "a window query that writes a table is not supported");
+  if (writes && !ins.empty()) fail(CEP_E_UNSUPPORTED, what + "`in` in a query that writes a table is not supported");
+  if (!q.group_by.empty() || q.having)
+    fail(CEP_E_UNSUPPORTED, what + "group by / having in a query on a table is not supported");
+  for (auto& it : q.select)
+    if (has_call(it.e)) fail(CEP_E_UNSUPPORTED, what + "aggregates in a query on a table are not supported");
+
+  const int ti = app->table_index(tid);
+  const StreamSchema T = app->tables[ti].schema;
+  const int pk = app->tables[ti].pk;
+  const std::string pkn = T.attrs[pk].name;
+  const bool join = t1 || t2;
+  const std::string& sname = t1 ? q.stream2 : q.stream;
+  const std::string& salias = t1 ? q.alias2 : q.alias;
+  const int si = app->input_index(sname);
+  if (si < 0) fail(CEP_E_UNDEFINED_STREAM, "stream " + sname + " is not defined");
+  if (si >= 8) fail(CEP_E_UNSUPPORTED, what + "table operations over more than 8 streams are not supported");
+  const StreamSchema sd = app->inputs[si];
+
+  Query out;
+  out.kind = Q_TABLE;
+  out.in_stream = si;
+  out.tab = ti;
+  for (int w = 0; w < kMaxCaps; ++w) out.tab_ins[w] = out.tab_set[w] = -1;
+  Loader raw{[](const Expr& e) { return std::make_pair((uint8_t)OP_LDCOL, (uint32_t)e.col); }};
+  auto same_key_type = [&](int col) {
+    if (sd.attrs[col].type != T.attrs[pk].type)
+      fail(CEP_E_PARSE, what + "attribute " + sd.attrs[col].name + " (" + type_name(sd.attrs[col].type) +
+                            ") does not have the type of the primary key " + pkn + " (" + type_name(T.attrs[pk].type) + ")");
+  };
+  auto is_pk = [&](const ExprP& e, const std::string& alias) {
+    return e->k == Expr::ATTR && e->idx == -1 && (e->ref == tid || (!alias.empty() && e->ref == alias)) && e->name == pkn;
+  };
+
+  if (join) {
+    // ---- lookup join: state 0 = the stream row, state 1 = the table row
+    const auto& tfilters = t1 ? q.filters : q.filters2;
+    const int twin = t1 ? q.win_kind : q.win_kind2;
+    const std::string& talias = t1 ? q.alias : q.alias2;
+    auto& sfilters = t1 ? q.filters2 : q.filters;
+    if (!tfilters.empty() || twin != WIN_NONE)
+      fail(CEP_E_UNSUPPORTED, what + "a window or filter on the table side of a join is not supported");
+    if ((t1 ? q.win_kind2 : q.win_kind) != WIN_NONE)
+      fail(CEP_E_UNSUPPORTED, what + "a window on the stream side of a join against a table is not supported "
+                                     "(only the stream's rows trigger, each against the table as it stands)");
+    if (!q.win_events.empty() && q.win_events != "current")
+      fail(CEP_E_UNSUPPORTED, what + "insert " + q.win_events + " events on a join against a table is not supported");
+    if (q.select_all) fail(CEP_E_PARSE, "join query needs an explicit select");
+    Ctx c;
+    c.mode = Ctx::PATTERN;
+    c.states = {&sd, &T};
+    c.aliases = {salias.empty() ? sname : salias, talias.empty() ? tid : talias};
+    if (c.aliases[0] == c.aliases[1]) fail(CEP_E_PARSE, "duplicate alias " + c.aliases[0] + " in join");
+    for (auto& f : sfilters) {
+      c.cur_state = 0;
+      bind_expr(f, c, app);
+      if (f->t != T_BOOL) fail(CEP_E_PARSE, "filter condition must be bool");
+      std::vector<std::pair<int, int>> refs;
+      collect_refs(f, &refs);
+      for (auto& r : refs)
+        if (r.first != 0) fail(CEP_E_PARSE, "a join side's filter reads the other side (" + c.aliases[r.first] + ")");
+    }
+    out.filter = compile_and(app, sfilters, raw);
+    out.filter_terms = lower_terms(sfilters);
+    c.cur_state = -1;
+    const std::string need = "`on` of a join against a table must hold exactly one conjunct <stream attribute> == " +
+                             tid + "." + pkn + " (a table is addressed by its primary key only)";
+    if (!q.on) fail(CEP_E_UNSUPPORTED, what + need);
+    bind_expr(q.on, c, app);
+    if (q.on->t != T_BOOL) fail(CEP_E_PARSE, "join `on` condition must be bool");
+    std::vector<ExprP> atoms, rest;
+    flatten(q.on, "and", &atoms);
+    int nkey = 0;
+    for (auto& e : atoms) {
+      bool key = e->k == Expr::BIN && e->op == "==" && e->args[0]->k == Expr::ATTR && e->args[1]->k == Expr::ATTR &&
+                 e->args[0]->idx == -1 && e->args[1]->idx == -1 && e->args[0]->state != e->args[1]->state;
+      if (key) {
+        const ExprP& et = e->args[e->args[0]->state == 1 ? 0 : 1];
+        const ExprP& es = e->args[e->args[0]->state == 1 ? 1 : 0];
+        key = et->col == pk;
+        if (key) {
+          same_key_type(es->col);
+          out.tab_key_col = es->col;
+          ++nkey;
+        }
+      }
+      if (!key) rest.push_back(e);
+    }
+    if (nkey != 1) fail(CEP_E_UNSUPPORTED, what + need);
+    std::set<std::string> names;
+    for (auto& it : q.select) {
+      bind_expr(it.e, c, app);
+      if (it.e->t == T_OBJECT) fail(CEP_E_UNSUPPORTED, "object attributes in select");
+      if (!names.insert(it.name).second) fail(CEP_E_PARSE, "duplicate output attribute " + it.name);
+    }
+    // stream attributes load by raw column here; finish_tables maps them to carried words
+    Loader jl{[](const Expr& e) {
+      return std::make_pair((uint8_t)(e.state == 0 ? OP_LDCOL : OP_LDCAP), (uint32_t)e.col);
+    }};
+    out.tab_on = compile_and(app, rest, jl);
+    for (auto& it : q.select) {
+      OutItem oi;
+      oi.name = it.name;
+      oi.type = it.e->t;
+      CodeGen cg(app, jl);
+      oi.prog = cg.compile(it.e);
+      oi.src = direct_source(app, oi.prog);   // SRC_REC + column (stream row), SRC_CAP + attribute (table row)
+      out.select.push_back(oi);
+    }
+    out.tab_op = TOP_JOIN;
+    out.out_stream = q.out;
+    add_output(app, q.out, out.select);
+  } else {
+    Ctx c;
+    c.mode = Ctx::SINGLE;
+    c.single = &sd;
+    c.single_id = q.stream;
+    c.single_alias = q.alias;
+    // the filter's top-level conjuncts; the `in` conjunct is the operation itself
+    std::vector<ExprP> atoms, own;
+    for (auto& f : q.filters) flatten(f, "and", &atoms);
+    ExprP in;
+    int nin = 0;
+    for (auto& e : atoms) {
+      const ExprP& x = e->k == Expr::NOT ? e->args[0] : e;
+      if (x->k == Expr::IN) {
+        in = x;
+        out.tab_negate = e->k == Expr::NOT;
+        ++nin;
+      } else {
+        own.push_back(e);
+      }
+    }
+    if (!writes) {
+      if (nin != 1 || ins.size() != 1)
+        fail(CEP_E_UNSUPPORTED, what + "`in` is supported only as exactly one top-level `and` conjunct (or its `not`) "
+                                       "of a filter");
+      if (q.win_kind != WIN_NONE) fail(CEP_E_UNSUPPORTED, what + "a window on a query with `in` is not supported");
+      const ExprP& cnd = in->args[0];
+      const bool shape = cnd->k == Expr::BIN && cnd->op == "==" && cnd->args[0]->k == Expr::ATTR &&
+                         cnd->args[1]->k == Expr::ATTR;
+      int side = -1;
+      if (shape && is_pk(cnd->args[0], "")) side = 1;
+      else if (shape && is_pk(cnd->args[1], "")) side = 0;
+      if (side < 0)
+        fail(CEP_E_UNSUPPORTED, what + "the condition of `in` must be the primary-key equality " + tid + "." + pkn +
+                                    " == <attribute> (a table is addressed by its primary key only)");
+      bind_expr(cnd->args[side], c, app);
+      same_key_type(cnd->args[side]->col);
+      out.tab_key_col = cnd->args[side]->col;
+      out.tab_op = TOP_IN;
+    }
+    for (auto& f : own) {
+      bind_expr(f, c, app);
+      if (f->t != T_BOOL) fail(CEP_E_PARSE, "filter condition must be bool");
+    }
+    out.filter = compile_and(app, own, raw);
+    out.filter_terms = lower_terms(own);
+    if (q.select_all) {
+      q.select.clear();
+      for (auto& a : sd.attrs) {
+        SelItem it;
+        it.e = std::make_shared<Expr>();
+        it.e->k = Expr::ATTR;
+        it.e->name = a.name;
+        it.name = a.name;
+        q.select.push_back(it);
+      }
+    }
+    std::set<std::string> names;
+    for (auto& it : q.select) {
+      if (writes && (it.e->k != Expr::ATTR || it.e->idx != -1))
+        fail(CEP_E_UNSUPPORTED, what + "a computed select item in a query that writes a table is not supported "
+                                       "(select plain attributes)");
+      bind_expr(it.e, c, app);
+      if (it.e->t == T_OBJECT) fail(CEP_E_UNSUPPORTED, "object attributes in select");
+      if (!names.insert(it.name).second) fail(CEP_E_PARSE, "duplicate output attribute " + it.name);
+    }
+    if (!writes) {
+      for (auto& it : q.select) {
+        OutItem oi;
+        oi.name = it.name;
+        oi.type = it.e->t;
+        CodeGen cg(app, raw);
+        oi.prog = cg.compile(it.e);
+        oi.src = direct_source(app, oi.prog);   // SRC_REC + column; finish_tables maps it to the carried word
+        out.select.push_back(oi);
+      }
+      out.out_stream = q.out;
+      add_output(app, q.out, out.select);
+    } else {
+      // ---- writers: select items are plain attributes, addressed by name
+      auto item_of = [&](const std::string& n) {
+        for (size_t i = 0; i < q.select.size(); ++i)
+          if (q.select[i].name == n) return (int)i;
+        return -1;
+      };
+      auto is_item = [&](const ExprP& e) {
+        return e->k == Expr::ATTR && e->idx == -1 && (e->ref.empty() || e->ref == q.stream || e->ref == q.alias) &&
+               item_of(e->name) >= 0;
+      };
+      // `on T.<pk> == <select item name>`, either order -> the item
+      auto key_item = [&]() {
+        const ExprP& e = q.out_on;
+        const bool shape = e && e->k == Expr::BIN && e->op == "==";
+        if (shape && is_pk(e->args[0], "") && is_item(e->args[1])) return item_of(e->args[1]->name);
+        if (shape && is_pk(e->args[1], "") && is_item(e->args[0])) return item_of(e->args[0]->name);
+        fail(CEP_E_UNSUPPORTED, what + "`on` must be the primary-key equality " + tid + "." + pkn +
+                                    " == <select item name> (a table is addressed by its primary key only)");
+      };
+      auto typed = [&](int w, int item) {
+        if (q.select[item].e->t != T.attrs[w].type)
+          fail(CEP_E_PARSE, what + "select item " + q.select[item].name + " (" + type_name(q.select[item].e->t) +
+                                ") does not have the type of attribute " + T.attrs[w].name + " (" +
+                                type_name(T.attrs[w].type) + ")");
+      };
+      const bool ins_row = q.out_kind == QueryAst::OUT_INSERT || q.out_kind == QueryAst::OUT_UPSERT;
+      int kitem = -1;
+      if (ins_row) {
+        // the select list is the table's row
+        if (q.select.size() != T.attrs.size())
+          fail(CEP_E_PARSE, what + "the select list has " + std::to_string(q.select.size()) + " items, the table " +
+                                std::to_string(T.attrs.size()) + " attributes");
+        for (size_t w = 0; w < T.attrs.size(); ++w) typed((int)w, (int)w);
+        for (size_t w = 0; w < T.attrs.size(); ++w)
+          if (q.select[w].name != T.attrs[w].name)
+            fail(CEP_E_UNSUPPORTED, what + "select item " + q.select[w].name + " is stored as attribute " +
+                                        T.attrs[w].name + ": items of a query that inserts into a table must carry "
+                                        "the table's attribute names");
+        for (size_t w = 0; w < T.attrs.size(); ++w) out.tab_ins[w] = q.select[w].e->col;
+        kitem = pk;
+      }
+      if (q.out_kind != QueryAst::OUT_INSERT) {
+        const int ki = key_item();
+        if (ins_row && ki != pk)
+          fail(CEP_E_UNSUPPORTED, what + "`on` of update or insert must compare the primary key with the select item "
+                                         "that is stored as the primary key");
+        kitem = ki;
+      }
+      if (q.out_kind == QueryAst::OUT_UPSERT || q.out_kind == QueryAst::OUT_UPDATE) {
+        if (!q.out_set.empty()) {
+          for (auto& st : q.out_set) {
+            const ExprP& l = st.first;
+            const int w = (l->k == Expr::ATTR && l->idx == -1 && (l->ref.empty() || l->ref == tid)) ? T.index(l->name) : -1;
+            if (w < 0) fail(CEP_E_PARSE, what + "`set` names an attribute that is not in the table");
+            if (w == pk) fail(CEP_E_UNSUPPORTED, what + "`set` of the primary key is not supported");
+            if (!is_item(st.second))
+              fail(CEP_E_UNSUPPORTED, what + "`set` takes plain select item names on the right-hand side");
+            const int it = item_of(st.second->name);
+            typed(w, it);
+            out.tab_set[w] = q.select[it].e->col;
+          }
+        } else {
+          for (size_t w = 0; w < T.attrs.size(); ++w) {
+            const int it = item_of(T.attrs[w].name);
+            if (it < 0)
+              fail(CEP_E_PARSE, what + "update without `set` needs every table attribute in the select list (" +
+                                    T.attrs[w].name + " is missing)");
+            typed((int)w, it);
+            // (the key's own word already holds the key)
+            if ((int)w != pk) out.tab_set[w] = q.select[it].e->col;
+          }
+        }
+      }
+      same_key_type(q.select[kitem].e->col);
+      out.tab_key_col = q.select[kitem].e->col;
+      out.tab_op = q.out_kind == QueryAst::OUT_INSERT ? TOP_INSERT
+                 : q.out_kind == QueryAst::OUT_UPSERT ? TOP_UPSERT
+                 : q.out_kind == QueryAst::OUT_UPDATE ? TOP_UPDATE : TOP_DELETE;
+    }
+  }
+  out.group_cols = {out.tab_key_col};   // the routing key of the stream (cep_plan_partition_keys)
+  app->tables[ti].ops.push_back((int)app->queries.size());
+  app->queries.push_back(out);
+  return true;
+}
+
+// After every query is compiled: each table's record layout (the union of
+// what its operations read, per stream) and the operations' programs mapped
+// from raw columns to carried words.
+void finish_tables(CompiledApp* app) {
+  for (auto& T : app->tables) {
+    const std::string what = "table " + T.schema.id + ": ";
+    if (T.ops.empty()) continue;
+    if ((int)T.ops.size() > kTabMaxOps)
+      fail(CEP_E_UNSUPPORTED, what + "more than " + std::to_string(kTabMaxOps) + " operations on one table are not supported");
+    T.a_stream = app->queries[T.ops[0]].in_stream;
+    int other = -1;
+    for (int qi : T.ops) {
+      Query& q = app->queries[qi];
+      const int s = q.in_stream;
+      if (T.key_col_s[s] >= 0 && T.key_col_s[s] != q.tab_key_col)
+        fail(CEP_E_UNSUPPORTED, what + "operations that key stream " + app->inputs[s].id +
+                                    " by different attributes are not supported");
+      T.key_col_s[s] = q.tab_key_col;
+      if (s != T.a_stream) {
+        if (other >= 0 && s != other && !same_types(app->inputs[s], app->inputs[other]))
+          fail(CEP_E_UNSUPPORTED, what + "operations over more than two streams need identical definitions of the "
+                                         "streams after the first");
+        if (other < 0) other = s;
+      }
+      // the columns this operation reads in the walk
+      std::vector<int> cols;
+      for (auto& it : q.select) collect_cols(app, it.prog, &cols);
+      collect_cols(app, q.tab_on, &cols);
+      for (int w = 0; w < kMaxCaps; ++w)
+        for (int c : {q.tab_ins[w], q.tab_set[w]})
+          if (c >= 0) index_of(cols, c, true);
+      std::vector<int>& list = s == T.a_stream ? T.rec_a : T.rec_b;
+      for (int c : cols) index_of(list, c, true);
+      if ((int)list.size() > kMaxCaps)
+        fail(CEP_E_UNSUPPORTED, what + "operations reading more than " + std::to_string(kMaxCaps) +
+                                    " attributes of stream " + app->inputs[s].id + " are not supported");
+    }
+    for (int qi : T.ops) {
+      Query& q = app->queries[qi];
+      std::vector<int>& list = q.in_stream == T.a_stream ? T.rec_a : T.rec_b;
+      for (auto& it : q.select) {
+        const Ins first = app->code[it.prog.off];
+        it.prog = remap_cols(app, it.prog, list);
+        if (it.src >= SRC_REC && it.src < SRC_TS) it.src = SRC_REC + index_of(list, (int)first.imm, false);
+      }
+      q.tab_on = remap_cols(app, q.tab_on, list);
+      for (int w = 0; w < kMaxCaps; ++w) {
+        if (q.tab_ins[w] >= 0) q.tab_ins[w] = index_of(list, q.tab_ins[w], false);
+        if (q.tab_set[w] >= 0) q.tab_set[w] = index_of(list, q.tab_set[w], false);
+      }
+      q.rec_cols_a = list;
+    }
+  }
+}
+
 // Query chaining.  A query whose output stream some query reads is a producer;
 // the streams it feeds are derived.  Checks what the engine's views cannot do
 // and records, per query, the producers behind the derived streams it reads.
@@ -1857,6 +2366,9 @@ void resolve_chains(CompiledApp* app) {
     const int m = app->input_index(q.out_stream);
     if (m < 0 || !read[m]) continue;   // an output nobody reads
     const std::string what = "stream " + q.out_stream + " is read by another query: its producer ";
+    if (q.kind == Q_TABLE)
+      fail(CEP_E_UNSUPPORTED, what + "must be a plain filter / projection query, not a query on a table (a derived "
+                                     "stream fed from a table lookup is not supported)");
     if (q.kind == Q_JOIN)
       fail(CEP_E_UNSUPPORTED, what + "must be a plain filter / projection query, not a join (chaining a join's "
                                      "output is not supported)");
@@ -1915,6 +2427,9 @@ void resolve_chains(CompiledApp* app) {
         up(s);
       }
     if (!any) continue;
+    if (q.kind == Q_TABLE)
+      fail(CEP_E_UNSUPPORTED, "table " + app->tables[q.tab].schema.id + ": a table operation on a derived stream (the "
+                              "output of another query) is not supported");
     if (q.kind == Q_JOIN)
       fail(CEP_E_UNSUPPORTED, "a join that reads a derived stream (the output of another query) is not supported");
     for (int s : reads)
@@ -2007,17 +2522,21 @@ int compile_app(const std::string& text, CompiledApp* out, std::string* err,
     CompiledApp app;
     if (dict_seed) app.strings = *dict_seed;
     std::vector<QueryAst> qs;
-    Parser(text).parse(&app.inputs, &qs);
+    std::vector<TableAst> tabs;
+    Parser(text).parse(&app.inputs, &qs, &tabs);
+    define_tables(&app, tabs);
     for (auto& q : qs) {
       if (q.single) app.read_ids.push_back(q.stream);
       if (q.join) app.read_ids.push_back(q.stream2);
       for (auto& st : q.states) app.read_ids.push_back(st.stream);
     }
     for (auto& q : qs) {
+      if (compile_table_query(&app, q)) continue;   // an operation on an event table
       if (q.join) compile_join(&app, q);
       else if (q.single) compile_single(&app, q);
       else compile_pattern(&app, q);
     }
+    finish_tables(&app);
     resolve_chains(&app);
     *out = std::move(app);
     return CEP_OK;

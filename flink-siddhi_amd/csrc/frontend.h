@@ -6,8 +6,9 @@
 //   SiddhiAppRuntime.getStreamDefinitionMap for output-type inference
 //                                         (SiddhiTypeFactory.java:64-112)
 // Unsupported-but-valid SiddhiQL (outer / unidirectional joins, windows other
-// than sliding #window.length / #window.time, tables, extensions) fails
-// with CEP_E_UNSUPPORTED so the Java shim can fall back to real Siddhi.
+// than sliding #window.length / #window.time, tables without a primary key or
+// addressed by anything but that key, extensions) fails with
+// CEP_E_UNSUPPORTED so the Java shim can fall back to real Siddhi.
 #pragma once
 #include <map>
 #include <string>
@@ -32,7 +33,7 @@ struct StreamSchema {
   }
 };
 
-enum QueryKind { Q_FILTER = 0, Q_PATTERN = 1, Q_AGG = 2, Q_JOIN = 3 };
+enum QueryKind { Q_FILTER = 0, Q_PATTERN = 1, Q_AGG = 2, Q_JOIN = 3, Q_TABLE = 4 };
 
 
 struct AggSpec {
@@ -129,6 +130,23 @@ struct Query {
   int join_nterms = -1;          // >= 0: `on` as direct comparisons (join_terms), -1: interpreter only
   JoinTerm join_terms[kMaxTerms];
 
+  // ---- event-table operation (Q_TABLE, tab_kernels.hip): a
+  // writer (`insert into T`, `update or insert into T`, `update T`, `delete
+  // T`: no output stream) or a reader (lookup join, `in`) over in_stream.
+  // `filter` is the operation's own-row filter over raw columns (without the
+  // `in` conjunct).  Rows of in_stream carry rec_cols_a in the table
+  // pipeline's records (TableDef::rec of the stream); tab_on and the select
+  // programs read carried word w of the stream row as LDCOL w (SRC_REC + w)
+  // and attribute w of the table row as LDCAP w (SRC_CAP + w).
+  int tab = -1;                  // index into CompiledApp::tables
+  int tab_op = -1;               // TabOpKind
+  int tab_key_col = -1;          // column of in_stream that equals the primary key
+  bool tab_negate = false;       // TOP_IN under `not`
+  Prog tab_on;                   // TOP_JOIN: the `on` conjuncts beside the key equality (invalid: none)
+  // writers, per table attribute w: the carried word stored when the key is
+  // absent (tab_ins) / present (tab_set); -1: none
+  int tab_ins[kMaxCaps], tab_set[kMaxCaps];
+
   // ---- query chaining (derive.hip): the query reads derived streams through
   // view `view` of CompiledApp::views (-1: it reads the batch as sent)
   int view = -1;
@@ -152,6 +170,19 @@ struct View {
   int stages = 0;
 };
 
+// `@PrimaryKey('k') define table T (...)`: per-key state of one pipeline that
+// holds every operation on T (plan order).
+struct TableDef {
+  StreamSchema schema;
+  int pk = -1;                   // primary-key attribute
+  std::vector<int> ops;          // query indices (Q_TABLE), plan order
+  // records: rows of stream a_stream carry rec_a, rows of every other stream
+  // rec_b (k_partition's two carried-column lists)
+  int a_stream = -1;
+  std::vector<int> rec_a, rec_b;
+  int key_col_s[8];              // per input handle: the column that maps to the key (-1)
+};
+
 constexpr int kMaxChainDepth = 4;
 constexpr int kMaxDerived = 8;
 constexpr int kMaxStageProducers = 4;   // producers sharing one k_derive pass
@@ -166,6 +197,7 @@ struct CompiledApp {
   std::vector<Derived> derived;         // query chaining: producers of read derived streams
   std::vector<View> views;
   std::vector<std::string> read_ids;    // stream ids the plan's queries read (compile_app)
+  std::vector<TableDef> tables;         // event tables, definition order
 
   int input_index(const std::string& id) const {
     for (size_t i = 0; i < inputs.size(); ++i)
@@ -176,6 +208,11 @@ struct CompiledApp {
     for (auto& d : derived)
       if (d.stream == handle) return true;
     return false;
+  }
+  int table_index(const std::string& id) const {
+    for (size_t i = 0; i < tables.size(); ++i)
+      if (tables[i].schema.id == id) return (int)i;
+    return -1;
   }
   int output_index(const std::string& id) const {
     for (size_t i = 0; i < outputs.size(); ++i)

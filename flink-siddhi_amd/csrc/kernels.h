@@ -313,6 +313,53 @@ struct WinArgs {
   unsigned int* err;
 };
 
+// ------------------------------------------- event tables (tab_kernels.hip) --
+// `@PrimaryKey('k') define table T (...)` with its writers (insert, update or
+// insert, update, delete) and readers (lookup join, `in`): DESIGN §11.  One
+// pipeline per table.  k_partition runs unchanged in its N-state record form:
+// operation j stands where state j stands (pat.st_stream[j], pat.st_raw[j] =
+// the operation's own-row filter), role bit j of a record = the row passed
+// operation j's filter, pat.key_col_s[stream] = the column that maps to the
+// primary key.  k_tabwalk: one workgroup per key bucket, one lane per key;
+// the lane holds the key's row in registers and applies the set role bits of
+// each of the key's records in arrival order, then plan order.
+// State, in the WalkArgs layout over the bucket-major key index:
+//   thdr[idx]                 bit 0: the key holds a row
+//   tword[w * kstride + idx]  attribute w of the row (VM word: int sign-extended, ...)
+struct TabOp {
+  int32_t kind;                  // TabOpKind
+  int32_t negate;                // TOP_IN under `not`
+  int32_t on_prog;               // TOP_JOIN: the `on` conjuncts beside the key equality (-1: none)
+  int32_t reader;                // 1: lookup join / `in` (TabArgs::out[j] is its output)
+  // writers, per table attribute w: carried record word stored when the key
+  // is absent (ins) / present (set); -1: none
+  int32_t ins[kMaxCaps], set[kMaxCaps];
+};
+struct TabArgs {
+  VmArgs vm;
+  PatternArgs pat;
+  int32_t nops, nwords;          // operations; attributes of the table
+  int32_t nreaders;
+  TabOp op[kTabMaxOps];
+  const uint64_t* recs;          // k_partition's output, unchanged
+  const uint16_t* tile_off;
+  int32_t ntiles;
+  int32_t tile_rows;
+  const int64_t* chunk_base;
+  uint32_t* thdr;
+  uint64_t* tword;
+  int64_t kstride;
+  // per operation (readers): its output stream and select list; src is
+  // SRC_REC + w (carried word of the stream row), SRC_CAP + w (table
+  // attribute) or SRC_VM.  Readers of one stream share its cursor.
+  OutArgs out[kTabMaxOps];
+  unsigned long long* dropped;   // inserts dropped on an existing key
+  unsigned int* err;
+};
+static_assert(sizeof(TabArgs) <= 4096, "TabArgs must fit the kernel argument segment");
+// vm: some reader has `on` conjuncts beside the key equality or a computed select item
+void launch_tabwalk(const TabArgs& a, int nbuckets, bool vm, hipStream_t s);
+
 // ------------------------------------- windowed stream joins (join_kernels.hip) --
 // `from A[f]#window.wa as a join B[g]#window.wb as b on C select ...` (DESIGN
 // §10).  Per side a device list of kept rows in arrival order, entry =

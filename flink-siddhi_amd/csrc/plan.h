@@ -109,6 +109,21 @@ struct JoinTerm {
   int32_t op, type;
 };
 
+// Event tables (tab_kernels.hip): a table with a primary key, addressed only
+// by that key.  One operation per query that names the table; a table's
+// operations share one pipeline and apply to a key's row in arrival order,
+// then plan order.
+constexpr int kTabMaxOps = 6;     // operations per table (role bits of a record)
+constexpr int kMaxTables = 4;     // tables per app
+enum TabOpKind : int32_t {
+  TOP_INSERT = 0,   // store the row when the key is absent, else drop it (counted)
+  TOP_UPSERT = 1,   // `update or insert`
+  TOP_UPDATE = 2,   // overwrite when the key is present
+  TOP_DELETE = 3,   // remove when the key is present
+  TOP_JOIN = 4,     // lookup join: one output row when the key is present (and C holds)
+  TOP_IN = 5,       // `(T.k == x) in T` / `not (... in T)` as a filter conjunct
+};
+
 // Role bits carried in partition records (pattern path).
 enum : uint32_t {
   ROLE_A = 1u,        // event passes the start state's filter f

@@ -30,7 +30,7 @@ NUMPY_DTYPES = {INT: "int32", LONG: "int64", FLOAT: "float32",
                 DOUBLE: "float64", BOOL: "uint8", STRING: "int32"}
 
 (K_FILTER, K_PARTITION, K_WALK, K_ROUTE, K_ORDER, K_AGG, K_OTHER, K_CF_PARTITION, K_CF_WALK, K_HOT,
- K_MQ_PARTITION, K_MQ_WALK, K_CF_PARTITION_2WG, K_JOIN, K_JOIN_VM) = range(15)
+ K_MQ_PARTITION, K_MQ_WALK, K_CF_PARTITION_2WG, K_JOIN, K_JOIN_VM, K_TABLE) = range(16)
 
 
 # ---- exceptions mirroring the reference ---------------------------------
@@ -55,8 +55,8 @@ class DuplicatedStreamException(SiddhiError):
 
 
 class UnsupportedPlanException(SiddhiError):
-    """Valid SiddhiQL outside the device subset: joins, tables, stream
-    functions, and every window but the sliding `#window.length(N)` /
+    """Valid SiddhiQL outside the device subset: outer joins, tables without a
+    primary key or addressed by anything but that key, stream functions, and every window but the sliding `#window.length(N)` /
     `#window.time(T)` aggregates whose window instance is the aggregate group
     (batch / external-time windows, a length window shared by several groups,
     a filter after the window, expired-event output; include/cep.h)."""
@@ -122,7 +122,8 @@ class cep_stats_t(C.Structure):
     _fields_ = [("events_in", C.c_int64), ("matches_out", C.c_int64),
                 ("batches", C.c_int64), ("kernel_launches", C.c_int64 * 16),
                 ("kernel_ms", C.c_double * 16), ("kernel_timed", C.c_int64 * 16),
-                ("late_events", C.c_int64), ("hot_keys", C.c_int64)]
+                ("late_events", C.c_int64), ("hot_keys", C.c_int64),
+                ("table_dropped", C.c_int64), ("table_vm_launches", C.c_int64)]
 
 
 EMIT_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(cep_rows))
@@ -159,6 +160,7 @@ SIGNATURES = {
     "cep_dict_lookup": (C.c_char_p, [C.c_void_p, C.c_int32]),
     "cep_stats": (C.c_int, [C.c_void_p, C.POINTER(cep_stats_t)]),
     "cep_last_error": (C.c_char_p, [C.c_void_p]),
+    "cep_table_rows": (C.c_int, [C.c_void_p, C.c_char_p, EMIT_FN, C.c_void_p]),
     "cep_record_words": (C.c_int, [C.c_void_p]),
     "cep_route_batch": (C.c_int, [C.c_void_p, C.POINTER(cep_batch), C.c_int, C.c_int64,
                                   C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),

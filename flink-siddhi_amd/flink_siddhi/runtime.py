@@ -499,6 +499,26 @@ class SiddhiAppRuntime:
         b = C.create_string_buffer(data, len(data))
         self._check(self._lib.cep_restore(self._h, b, len(data)))
 
+    def table_rows(self, table_id: str) -> List[tuple]:
+        """The live rows of an event table (cep_table_rows), ordered by primary
+        key, as tuples in the table's attribute order (strings as dictionary
+        ids).  On a shard: the keys the shard owns."""
+        plan_types = [t for _, t in self.stream_definition(table_id)]
+        out: List[tuple] = []
+
+        def cb(user, rows_p):
+            r = rows_p.contents
+            cols = []
+            for c, t in enumerate(plan_types):
+                dt = np.dtype(L.NUMPY_DTYPES[t])
+                buf = (C.c_char * (r.n * dt.itemsize)).from_address(r.cols[c])
+                cols.append(np.frombuffer(buf, dtype=dt).tolist())
+            out.extend(zip(*cols))
+
+        cfn = L.EMIT_FN(cb)
+        self._check(self._lib.cep_table_rows(self._h, table_id.encode(), cfn, None))
+        return out
+
     def stats(self) -> L.cep_stats_t:
         s = L.cep_stats_t()
         self._check(self._lib.cep_stats(self._h, C.byref(s)))

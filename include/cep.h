@@ -69,6 +69,42 @@
  * expired / all events`; at cep_create: key_stride > 1 (global windows cannot
  * be sharded by key); at the call: cep_route_* of an app that holds a join.
  *
+ * Event tables: `@PrimaryKey('k') define table T (k int, ...)`, a table with
+ * one primary-key attribute (int, long or string, values in [0,
+ * key_capacity) like partition keys; at most 8 attributes, none an object),
+ * addressed only by that key.  Writers are plain filter / projection queries
+ * over one defined stream whose select items are plain attributes:
+ *   from U[f] select k, id, price insert into T;
+ *   from U[f] select k, id, price update or insert into T [set ...] on T.k == k;
+ *   from U[f] select k, price update T [set T.price = price, ...] on T.k == k;
+ *   from U[f] select k delete T on T.k == k;
+ * Readers are the lookup join, `from S[g] [as s] join T [as t] on s.k == t.k
+ * [and C] select ... insert into O` (sides in either order; exactly one `on`
+ * conjunct equates a stream attribute with the primary key, the others form
+ * one condition over both rows), and `(T.k == x) in T` or its `not` as one
+ * top-level `and` conjunct of a plain filter query's filter.  Rows are
+ * processed in arrival order and, for one row, the queries that read its
+ * stream run in plan order: a reader sees the writes of earlier arrivals and
+ * of earlier queries on the same row.  insert stores the row when the key is
+ * absent and otherwise drops it (the first row stays; counted in
+ * cep_stats_t.table_dropped, the flush does not fail); update or insert
+ * overwrites the `set` attributes (all without `set`) of a present key and
+ * stores the select row of an absent one; update and delete act on a present
+ * key only.  Only stream rows trigger a join: one output row, with the stream
+ * row's ts and arrival number, when the table holds its key and C holds
+ * (upstream Siddhi 4.x semantics).  A writer has no
+ * output stream: cep_set_callback / cep_plan_schema on a table id is
+ * CEP_E_UNDEFINED_STREAM; cep_table_rows() reads a table.  At most 4 tables
+ * per app and 6 operations per table.  CEP_E_UNSUPPORTED (the message names
+ * the table): a table without @PrimaryKey or with a composite key, @Index,
+ * @Store, an `on` that is not the key equality, outer / unidirectional joins
+ * against a table, a window on either side or a filter on the table side, a
+ * join of two tables, `from T ...`, a pattern, sequence, window or aggregate
+ * query that writes a table, a computed select item in a writer, a table
+ * operation inside `partition with` or on a derived stream, a table reader
+ * whose output another query reads, two tables in one query; at cep_create:
+ * sparse_keys = 1; at the call: cep_route_*, cep_record_words, cep_row_words.
+ *
  * Hot-key probe: a keyed `every A -> B` runtime on the closed-form path
  * walks its first 2^20 rows as a short chunk and waits for it once inside
  * that cep_send_batch() (its hot-key verdict decides the next chunk's
@@ -93,9 +129,12 @@ extern "C" {
  *                              SiddhiOperatorContext.java:151)
  *   CEP_E_DUPLICATED_STREAM-> exception/DuplicatedStreamException.java:20
  *   CEP_E_UNSUPPORTED      -> valid SiddhiQL outside the engine subset
- *                             (tables, outer / unidirectional joins and the
- *                             other join forms listed above, windows other
- *                             than sliding #window.length / #window.time):
+ *                             (tables without a primary key or addressed by
+ *                             anything but that key and the other table
+ *                             forms listed above, outer / unidirectional
+ *                             joins and the other join forms listed above,
+ *                             windows other than sliding #window.length /
+ *                             #window.time):
  *                             shim falls back to real Siddhi
  *   CEP_E_ARG              -> IllegalArgumentException
  *                             (operator/StreamOutputHandler.java:89)
@@ -260,6 +299,8 @@ typedef struct {
   int64_t kernel_timed[16];   /* launches kernel_ms covers (profile = k: every k-th) */
   int64_t late_events;        /* rows dropped by cep_watermark as late (ts before an earlier release) */
   int64_t hot_keys;           /* closed-form path: keys matched by the hot-key kernels (hot.hip) */
+  int64_t table_dropped;      /* event tables: `insert into T` rows dropped because the key was present */
+  int64_t table_vm_launches;  /* the CEP_K_TABLE launches that ran the interpreter build of k_tabwalk */
 } cep_stats_t;
 
 /* Kernel kinds indexing cep_stats_t arrays. */
@@ -271,7 +312,8 @@ enum {
   CEP_K_MQ_PARTITION = 10, CEP_K_MQ_WALK = 11, /* multi-query groups (k_mqpart / k_mqwalk) */
   CEP_K_CF_PARTITION_2WG = 12,                /* launches only: the CEP_K_CF_PARTITION launches that ran k_cfpart2 */
   CEP_K_JOIN = 13,                            /* windowed stream joins: every kernel of join_kernels.hip */
-  CEP_K_JOIN_VM = 14                          /* launches only: the join probe passes whose `on` ran on the interpreter */
+  CEP_K_JOIN_VM = 14,                         /* launches only: the join probe passes whose `on` ran on the interpreter */
+  CEP_K_TABLE = 15                            /* event tables: k_tabwalk (their partition pass counts as CEP_K_PARTITION) */
 };
 
 /* ---- plan-level calls (no device needed) ------------------------------ */
@@ -313,7 +355,8 @@ cep_app* cep_create(const char* plan, const cep_options* opt, char* err,
 /* SiddhiAppRuntime.shutdown() — AbstractSiddhiOperator.java:144-148 */
 void cep_destroy(cep_app* app);
 
-/* getStreamDefinitionMap().get(id) — AbstractSiddhiOperator.java:160-163 */
+/* getStreamDefinitionMap().get(id) — AbstractSiddhiOperator.java:160-163
+ * (an input, derived or output stream; also the attributes of a table) */
 int cep_stream_schema(cep_app* app, const char* stream_id, cep_attr* out,
                       int cap, int* n);
 
@@ -398,6 +441,13 @@ int32_t cep_dict_intern(cep_app* app, const char* s);
 const char* cep_dict_lookup(cep_app* app, int32_t id);
 
 int cep_stats(cep_app* app, cep_stats_t* out);
+
+/* The live rows of event table `table_id`, ordered by primary key: waits for
+ * the engine's stream, then calls `fn` (once; not at all for an empty table)
+ * with columns = the table's attributes and ts / seq NULL.  On a shard
+ * (key_stride > 1) it delivers the keys the shard owns.  Table contents are
+ * part of cep_snapshot(). */
+int cep_table_rows(cep_app* app, const char* table_id, cep_emit_fn fn, void* user);
 const char* cep_last_error(cep_app* app);
 
 /* ---- multi-GPU key shuffle (Flink keyBy / router/DynamicPartitioner.java:43-60,
