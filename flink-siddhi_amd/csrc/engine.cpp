@@ -11,76 +11,21 @@
 //     arena [tiles][2048 rows][rec_words] + tile offset table.
 // All work for a batch is enqueued on the app's HIP stream; cep_flush
 // synchronises, checks the device error word and delivers rows to callbacks.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <memory>
 #include <numeric>
-#include <string>
-#include <unordered_map>
-#include <vector>
 
-#include "../../include/cep.h"
-#include "frontend.h"
-#include "kernels.h"
+#include "rt.h"
+#include "snapshot.h"
 
 using namespace cep;
 
 namespace {
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
-bool dev_ensure(DevBuf* b, size_t bytes, hipStream_t s, bool keep) {
-  if (b->bytes >= bytes && b->p) return true;
-  size_t nb = std::max(bytes, b->bytes * 2);
-  void* p = nullptr;
-  if (hipMalloc(&p, nb) != hipSuccess) return false;
-  if (keep && b->p && b->bytes) hipMemcpyAsync(p, b->p, b->bytes, hipMemcpyDeviceToDevice, s);
-  if (b->p) {
-    hipStreamSynchronize(s);
-    hipFree(b->p);
+void set_err(char* err, size_t errlen, const std::string& m) {
+  if (err && errlen) {
+    std::snprintf(err, errlen, "%s", m.c_str());
   }
-  b->p = p;
-  b->bytes = nb;
-  return true;
-}
-
-void dev_free(DevBuf* b) {
-  if (b->p) hipFree(b->p);
-  b->p = nullptr;
-  b->bytes = 0;
-}
-
-// Pinned (page-locked) host memory: DMA at PCIe speed, no driver bounce.
-struct HostBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
-bool host_ensure(HostBuf* b, size_t bytes) {
-  if (b->bytes >= bytes && b->p) return true;
-  // pinning hundreds of MB takes ~100 ms: grow with headroom, so a delivery
-  // buffer sized by one flush's rows is not re-pinned when the next flush
-  // brings a few more
-  const size_t nb = std::max(bytes + bytes / 2, b->bytes * 2);
-  if (b->p) hipHostFree(b->p);
-  b->p = nullptr;
-  b->bytes = 0;
-  if (hipHostMalloc(&b->p, nb, hipHostMallocDefault) != hipSuccess) return false;
-  b->bytes = nb;
-  return true;
-}
-
-void host_free(HostBuf* b) {
-  if (b->p) hipHostFree(b->p);
-  b->p = nullptr;
-  b->bytes = 0;
 }
 
 bool is_pinned(const void* p) {
@@ -92,284 +37,9 @@ bool is_pinned(const void* p) {
   return at.type == hipMemoryTypeHost;
 }
 
-struct OutStream {
-  std::string id;
-  std::vector<int> types;
-  std::vector<DevBuf> cols;
-  DevBuf ts, seq;
-  unsigned long long* count = nullptr;   // device cursor
-  int64_t cap = 0;                       // allocated rows
-  int64_t bound = 0;                     // upper bound of rows since last flush
-  bool write_seq = true;                 // the kernels store arrival numbers (someone reads them)
-  cep_emit_fn fn = nullptr;
-  void* user = nullptr;
-  // pinned host copies for callback delivery (D2H at PCIe speed)
-  std::vector<HostBuf> hcols;
-  HostBuf hts, hseq;
-  // ordered_output: the rows permuted into Siddhi's emission order on the
-  // device (stable sort on seq) before the D2H
-  std::vector<DevBuf> scols;
-  DevBuf sts, sseq;
-};
-
-struct PatternRT {
-  int q = -1;
-  PatternArgs pa{};
-  DevBuf khdr, kslot;        // per-key state, SoA over the bucket-major key index
-  int64_t kstride = 0;       // keys_per_bucket * buckets
-  // double-buffered chunk arenas: partition(c+1) runs on the side stream
-  // while walk(c) runs on the main stream
-  DevBuf recs[2], tile_off[2], chunk_base[2];
-  hipEvent_t part_done[2] = {nullptr, nullptr}, walk_done[2] = {nullptr, nullptr};
-  PrefPlan pref;               // fast partition path (n < 0: generic)
-  bool used[2] = {false, false};
-  int cur = 0;                 // arena of the next chunk
-  int64_t chunk = 0;
-  int64_t chunk_tol = 0;       // chunk of the order-tolerant form (walked by the VM build: up to 16 Mi rows)
-  int64_t extra_bound = 0;   // pending partials that may still complete
-  bool part_vm = true;       // partition pass needs the interpreter
-  bool walk_vm = true;       // walk needs the interpreter (g on s1, computed select items)
-  // closed-form fast path (cf_kernels.hip): its own, larger chunk arenas
-  bool cf = false;
-  int64_t cf_chunk = 0;
-  DevBuf cf_recs[2], cf_toff[2];
-  // pending lists longer than S (closed-form path): per-key count + run
-  // offset, and two pools of overflow slots swapped per walk launch
-  DevBuf kext, pool[2], pool_cur;
-  int pool_side = 0;           // pool[pool_side] holds the current runs
-  int64_t pool_cap = 0;        // slots per pool
-  // sparse partition keys (cep_options.sparse_keys): value -> dense slot map
-  bool sparse = false;
-  uint64_t table_cap = 0;
-  DevBuf tkey, tval, krev, kcount, dense;
-  // hot keys (hot.hip): keys that would make their bucket a straggler are
-  // matched by grid-wide scans; the walk reports candidates, diversion starts
-  // (sticky) once the device has put a key into a hot slot
-  bool hot = false;            // candidate collection on (closed-form path, P + kCfHotMax buckets fit)
-  bool hot_on = false;         // diversion active: hot arenas allocated
-  // ts_order 0 on the closed form: in-order chunks take the adaptive build
-  // (CfPartArgs::atol); atol_ok goes false for good once another path has
-  // run the pattern (it keeps no high-water mark)
-  bool atol_ok = true;
-  uint32_t atol_seq = 0;       // gate value of the current adaptive chunk
-  int64_t tol_chunks = 0;      // high-water-mark shard set parity
-  DevBuf atol_gate;            // 64 B: the gate word
-  DevBuf hwm;                  // 2 x 64 u64: high-water-mark shard sets
-  bool hot_probed = false;     // the first (short) chunk ran and its candidates were read back
-  uint32_t hot_thresh = 0;     // records per key per launch that make a key hot
-  int hot_blocks = 0;
-  DevBuf hot_id, hot_key, hot_m, hot_gbase, hoff, cand, ncand, harr, hrow, hnb, bsum, bcnt, boff, hcm, hobase,
-      hot_active, htmn, htmx, hflag, btol;   // (the last four: order-tolerant runs)
-  HostBuf hot_active_host;     // pinned: slots in use (read without a sync)
-  hipEvent_t hot_fork = nullptr, hot_join = nullptr;   // hot kernels on the side stream, beside the walk
-  // a pattern whose result depends on event-time order (`within`, not a
-  // sequence): with cep_options.ts_order = 0 it runs the order-tolerant path
-  bool order_sensitive = false;
-  // sliding-window aggregate (win_kernels.hip): the window fields of WinArgs
-  // (kind, param, ring, entry layout); win.kind = WIN_NONE: not a window query
-  WinArgs win{};
-  bool win_vm = false;         // k_winwalk needs the interpreter (having, computed select items)
-};
-
-// Multi-query group (mq_kernels.hip): keyed queries of one app sharing a
-// key column, run by one partition pass + one walk per chunk.
-struct MqRT {
-  std::vector<int> qs;                   // query indices, plan order
-  std::vector<MqQuery> hq;               // host copy of the device descriptors
-  DevBuf dq, dconds;
-  std::vector<MqCond> conds;             // [8][kMqMaxCond]
-  int32_t ncond[8] = {0};
-  uint32_t stream_mask = 0;
-  int key_col = -1;
-  int view = -1;                         // query chaining: the view its queries read (-1: the batch)
-  std::vector<int> carry;                // logical carried columns
-  std::vector<int> cond_cols;            // columns the conditions read
-  bool check_order = false;
-  int64_t key_capacity = 0, kstride = 0;
-  int lg = 0, kpb = 0;
-  int key_stride = 1, key_offset = 0;
-  DevBuf state;
-  int64_t words = 0;                     // state words per key (all queries)
-  int64_t chunk = 0;
-  DevBuf recs[2], toff[2], chunk_base[2];
-  hipEvent_t part_done[2] = {nullptr, nullptr}, walk_done[2] = {nullptr, nullptr};
-  bool used[2] = {false, false};
-  int cur = 0;
-  bool dq_dirty = true;
-  std::vector<int> classes_kind, classes_n;   // shape classes in descriptor order (MqUnit kinds, sizes)
-  std::vector<MqUnit> units;
-  DevBuf du;
-};
-
-// Windowed stream join (join_kernels.hip): both sides' kept-row lists (double
-// buffered: k_jointail moves the surviving rows into the other buffer), the
-// chunk's flag / probe scratch and the device state words.
-struct JoinRT {
-  int q = -1;
-  JoinArgs ja{};               // the plan's part of the kernel arguments
-  bool mark_vm = false;        // a side filter needs the interpreter
-  bool on_vm = false;          // `on` needs the interpreter
-  bool sel_vm = false;         // a select item is computed
-  int64_t chunk = 0;
-  int64_t list_cap[2] = {0, 0};
-  DevBuf list[2][2];           // [side][buffer]
-  int cur = 0;                 // buffer holding the current lists
-  DevBuf flag, bsum, boff, probe, pcnt, pbsum, pboff, st;
-  HostBuf total;               // pinned: the chunk's row total (read back before the emit pass)
-};
-
-// Event table (tab_kernels.hip): one pipeline per table holding every
-// operation on it.  The generic partition pass (N-state record form: one
-// "state" per operation) and k_tabwalk, chunk by chunk, double buffered like a
-// pattern's arenas.  State: a present bit and the row's words per key.
-struct TableRT {
-  int tab = -1;                // index into CompiledApp::tables
-  int run_at = -1;             // query index at which the pipeline runs (its first reader, else its first operation)
-  PatternArgs pa{};            // k_partition's view of the operations
-  TabArgs ta{};                // the plan's part of the walk's arguments
-  bool vm = false;             // k_tabwalk needs the interpreter
-  DevBuf thdr, tword;
-  int64_t kstride = 0;
-  DevBuf recs[2], tile_off[2], chunk_base[2];
-  hipEvent_t part_done[2] = {nullptr, nullptr}, walk_done[2] = {nullptr, nullptr};
-  bool used[2] = {false, false};
-  int cur = 0;
-  int64_t chunk = 0;
-};
-
-struct TimedLaunch {
-  int kind;
-  hipEvent_t a, b;
-};
-
 }  // namespace
 
-struct cep_app {
-  CompiledApp app;
-  cep_options opt{};
-  hipStream_t stream = nullptr;
-  hipStream_t side = nullptr;    // partition pass of the next chunk
-  hipEvent_t in_ready = nullptr;
-  hipEvent_t ext_ready = nullptr;   // cep_stream_wait: producer stream of device inputs
-  hipEvent_t out_ready = nullptr;   // cep_stream_signal: the engine's work so far
-  // Shuffle sender (cep_route_batch of device batches) runs on its own stream:
-  // routing step s+1 overlaps the walk of step s (it touches no walk state)
-  hipStream_t rstream = nullptr;
-  hipEvent_t r_ready = nullptr;
-  hipEvent_t r_host = nullptr;     // a host batch's route (engine stream) joined into the route stream
-  bool enabled = true;
-  std::string last_error;
-  std::vector<std::string> dict;
-  std::unordered_map<std::string, int32_t> dict_index;
-  DevBuf code, konst;
-  std::vector<OutStream> outs;
-  std::vector<PatternRT> pats;
-  std::vector<MqRT> mqs;          // multi-query groups
-  std::vector<JoinRT> joins;      // windowed stream joins
-  std::vector<TableRT> tabs;      // event tables
-  DevBuf tab_dropped;             // inserts dropped on an existing key (device counter, every table)
-  std::vector<char> in_mq;        // per query: served by a multi-query group
-  DevBuf tile_state, ticket, err;
-  DevBuf route_arena, route_tcount, route_toffs, route_dcount;   // key shuffle (sender)
-  DevBuf rerr;                 // error word of the route kernels (route stream; the walk's is `err`)
-  DevBuf stamps;               // CEP_STAMPS=1: walk phase stamps (diagnostics)
-  DevBuf str_hash;             // Java String.hashCode per dictionary id (dynamic routing)
-  HostBuf flush_words;         // cep_flush: error word + output cursors + seq stats (pinned)
-  DevBuf out_counts;           // every output's row cursor (OutStream::count points here)
-  DevBuf ostats;               // cep_flush: per output {~min seq, max seq, descents} (k_seq_stats)
-  DevBuf okeys[2], oidx[2], otemp;   // cep_flush: emission-order sort scratch (shared by the outputs)
-  DevBuf rr_col[kMaxCols], rr_ts, rr_stream, rr_seq;   // cep_send_rows: unpacked rows
-  // query chaining: per view (CompiledApp::views) and stage, the handle column
-  // and the materialised columns of the last batch (stateless: rebuilt per batch)
-  struct ViewStage {
-    DevBuf stream, col[kMaxCols];
-  };
-  std::vector<std::vector<ViewStage>> views;
-  // host batches: two staging slots (pinned host arena + device arena); a
-  // batch's H2D copy runs on the copy stream while the previous batch's
-  // kernels run on the main stream
-  struct HostSlot {
-    HostBuf pinned;
-    DevBuf dev;
-    hipEvent_t dma_done = nullptr, free = nullptr;
-    bool used = false;
-  } hs[2];
-  int hs_next = 0;
-  hipStream_t copy = nullptr;
-  // event-time reorder buffer (cep_buffer_batch / cep_watermark): rows of
-  // one input layout since the last watermark, SoA in arrival order
-  struct Reorder {
-    int input = -1;            // layout owner (-1: empty)
-    bool has_stream = false;
-    int64_t n = 0, cap = 0;
-    int64_t released_max = INT64_MIN;   // latest ts handed to the engine
-    DevBuf col[kMaxCols], ts, stream;  // buffered rows
-    DevBuf out[kMaxCols], ots, ostream;   // sorted released rows (a device batch)
-    DevBuf keys, idx_in, idx_out, temp, bound;
-  } ro;
-  int64_t events_in = 0, matches_out = 0, batches = 0, late_events = 0;
-  int64_t tab_vm_launches = 0;   // k_tabwalk launches of the interpreter build
-  int64_t last_ts = INT64_MIN;
-  DevBuf last_ts_dev;          // last ts of the previous batch (RowsArgs::prev_ts_dev)
-  bool force_tolerant = false; // this batch holds late rows (cep_watermark, late_policy 2)
-  bool seq_poison = false;     // diagnostics (CEP_SEQ_POISON=1): unread seq columns hold a pattern the flush checks
-  bool cf_one_wg = false;      // CEP_CF_PART=1 (read at creation): k_cfpart where k_cfpart2 would run
-  int64_t launches[16] = {0};
-  double kernel_ms[16] = {0};
-  int64_t kernel_timed[16] = {0};
-  std::vector<TimedLaunch> timed;
-  std::vector<hipEvent_t> event_pool;
-  std::vector<std::unique_ptr<char[]>> name_store;
-};
-
-namespace {
-
-void set_err(char* err, size_t errlen, const std::string& m) {
-  if (err && errlen) {
-    std::snprintf(err, errlen, "%s", m.c_str());
-  }
-}
-
-int fail(cep_app* a, int code, const std::string& m) {
-  if (a) a->last_error = m;
-  return code;
-}
-
-hipEvent_t pool_event(cep_app* a) {
-  if (!a->event_pool.empty()) {
-    hipEvent_t e = a->event_pool.back();
-    a->event_pool.pop_back();
-    return e;
-  }
-  hipEvent_t e;
-  hipEventCreate(&e);
-  return e;
-}
-
-struct LaunchTimer {
-  cep_app* a;
-  int kind;
-  hipStream_t st;
-  hipEvent_t s = nullptr;
-  // profile = k: HIP events around every k-th launch of each kernel kind
-  // (each event between two kernels widens the gap between them by ~5 us)
-  LaunchTimer(cep_app* app, int k, hipStream_t on = nullptr)
-      : a(app), kind(k), st(on ? on : app->stream) {
-    const bool timed = a->opt.profile > 0 && a->launches[k] % a->opt.profile == 0;
-    a->launches[k]++;
-    if (timed) {
-      s = pool_event(a);
-      hipEventRecord(s, st);
-    }
-  }
-  ~LaunchTimer() {
-    if (s) {
-      hipEvent_t e = pool_event(a);
-      hipEventRecord(e, st);
-      a->timed.push_back({kind, s, e});
-    }
-  }
-};
+namespace cep {
 
 void harvest_timers(cep_app* a) {
   for (auto& t : a->timed) {
@@ -377,10 +47,33 @@ void harvest_timers(cep_app* a) {
     hipEventElapsedTime(&ms, t.a, t.b);
     a->kernel_ms[t.kind] += ms;
     a->kernel_timed[t.kind]++;
-    a->event_pool.push_back(t.a);
-    a->event_pool.push_back(t.b);
+    a->event_pool.push_back(std::move(t.a));
+    a->event_pool.push_back(std::move(t.b));
   }
   a->timed.clear();
+}
+
+hipStream_t ChunkPipe::open(cep_app* a) {
+  hipEventRecord(a->in_ready, a->stream);
+  hipStreamWaitEvent(a->side, a->in_ready, 0);
+  static const bool no_overlap = std::getenv("CEP_NO_OVERLAP") != nullptr;
+  events = true;
+  return no_overlap ? a->stream.h : a->side.h;
+}
+
+hipStream_t ChunkPipe::open_cf(cep_app* a) {
+  // Both passes on the main stream by default: k_cfpart and k_cfwalk cannot
+  // share a CU (each fills its register file), so the side stream only
+  // time-slices them (measured: no throughput gain, inflated kernel times).
+  // CEP_OVERLAP=1 puts the partition on the side stream.  Serial mode issues
+  // no cross-stream events: every event between two kernels of one stream
+  // costs a gap (rocprofv3 trace: ~15 us between k_cfpart and k_cfwalk).
+  static const bool overlap = std::getenv("CEP_OVERLAP") != nullptr;
+  events = overlap;
+  if (!overlap) return a->stream;
+  hipEventRecord(a->in_ready, a->stream);
+  hipStreamWaitEvent(a->side, a->in_ready, 0);
+  return a->side;
 }
 
 int ensure_out_cap(cep_app* a, OutStream& o, int64_t need) {
@@ -417,571 +110,6 @@ OutArgs out_args(OutStream& o, const Query& q) {
   return oa;
 }
 
-// ---- multi-query groups (mq_kernels.hip) ------------------------------------
-// A query joins a group when its per-event work is interpreter-free and keyed
-// on the group's key column: group-by aggregations (term-list filter, plain
-// column arguments, select items key / aggregate / column, having on one
-// output item) and sequences of the one-live-partial shape (a single start
-// event on a stream no later state reads) with own-column term-list
-// conditions and first / last captures.  Queries of one group share the
-// partition pass (one read of the batch, each distinct condition evaluated
-// once per row) and the walk (AbstractSiddhiOperator.java:283-287: every
-// event goes to every query).  CEP_NO_MQ=1: no groups (general path).
-bool same_layout(const CompiledApp& app, int s, int t) {
-  const auto& x = app.inputs[s].attrs;
-  const auto& y = app.inputs[t].attrs;
-  if (x.size() != y.size()) return false;
-  for (size_t c = 0; c < x.size(); ++c)
-    if (x[c].type != y[c].type) return false;
-  return true;
-}
-
-bool same_terms(const TermList& x, const TermList& y) {
-  if (x.n != y.n || x.any != y.any) return false;
-  for (int i = 0; i < x.n; ++i) {
-    const Term &u = x.t[i], &v = y.t[i];
-    if (u.col != v.col || u.coltype != v.coltype || u.aop != v.aop || u.atype != v.atype || u.aconst != v.aconst ||
-        u.cop != v.cop || u.ctype != v.ctype || u.cconst != v.cconst)
-      return false;
-  }
-  return true;
-}
-
-// What one query adds to a group: its conditions per stream, carried columns.
-struct MqNeeds {
-  int key_col = -1, layout = -1;
-  std::vector<std::pair<int, TermList>> conds;   // (stream, condition), n == 0: always true
-  std::vector<int> carry;                        // columns carried in records
-  std::vector<int> cols;                         // columns conditions read
-};
-
-bool mq_candidate(const cep_app* a, const Query& q, MqNeeds* nd) {
-  const CompiledApp& app = a->app;
-  if (a->opt.sparse_keys) return false;
-  auto key_ok = [&](int s, int col) {
-    if (s < 0 || col < 0) return false;
-    const int t = app.inputs[s].attrs[col].type;
-    return t == T_INT || t == T_LONG;
-  };
-  auto add_cols = [&](const TermList& tl) {
-    for (int i = 0; i < tl.n; ++i)
-      if (std::find(nd->cols.begin(), nd->cols.end(), tl.t[i].col) == nd->cols.end()) nd->cols.push_back(tl.t[i].col);
-  };
-  auto carry = [&](int col) {
-    if (col == nd->key_col) return;
-    if (std::find(nd->carry.begin(), nd->carry.end(), col) == nd->carry.end()) nd->carry.push_back(col);
-  };
-  if (q.kind == Q_AGG) {
-    // a windowed aggregate keeps a ring per key: its own pipeline (k_winwalk)
-    if (q.win_kind != WIN_NONE) return false;
-    if (q.in_stream < 0 || !key_ok(q.in_stream, q.key_col)) return false;
-    if ((int)q.aggs.size() > kMqMaxAggs || !q.having_simple || (int)q.select.size() > kMqMaxSel) return false;
-    if (q.f.valid() && q.f_terms.n < 0) return false;
-    nd->key_col = q.key_col;
-    nd->layout = q.in_stream;
-    TermList f;
-    f.n = 0;
-    if (q.f.valid()) f = q.f_terms;
-    nd->conds.push_back({q.in_stream, f});
-    add_cols(f);
-    for (auto& ag : q.aggs) {
-      if (ag.arg.valid() && ag.word < 0) return false;
-      if (ag.word >= 0) carry(q.rec_cols_a[ag.word]);
-    }
-    for (auto& it : q.select) {
-      if (it.src == SRC_KEY || (it.src >= SRC_AGG && it.src < SRC_AGG + (int)q.aggs.size())) continue;
-      if (it.src >= SRC_REC && it.src < SRC_REC + (int)q.rec_cols_a.size()) {
-        carry(q.rec_cols_a[it.src - SRC_REC]);
-        continue;
-      }
-      return false;
-    }
-    return true;
-  }
-  if (q.kind != Q_PATTERN || !q.nfa || !q.sequence) return false;
-  const int n = (int)q.nstates.size();
-  if (n < 1 || n > kMaxStates || q.nstates[0].min_count != 1 || q.nstates[0].max_count != 1) return false;
-  if ((int)q.ncaps.size() > kMqMaxCaps || (int)q.select.size() > kMqMaxSel) return false;
-  for (int j = 0; j < n; ++j) {
-    const auto& st = q.nstates[j];
-    if (j > 0 && st.stream == q.nstates[0].stream) return false;   // one live partial per key
-    if (st.walk.valid() || st.terms.n < 0 || st.min_count > 254 || st.max_count > 254) return false;
-    const int col = st.stream < (int)q.key_col_s.size() ? q.key_col_s[st.stream] : -1;
-    if (!key_ok(st.stream, col) || (nd->key_col >= 0 && col != nd->key_col)) return false;
-    if (!same_layout(app, st.stream, q.nstates[0].stream)) return false;
-    nd->key_col = col;
-  }
-  nd->layout = q.nstates[0].stream;
-  for (int j = 0; j < n; ++j) {
-    nd->conds.push_back({q.nstates[j].stream, q.nstates[j].terms});
-    add_cols(q.nstates[j].terms);
-  }
-  for (auto& cp : q.ncaps) {
-    if (cp.index != 0 && cp.index != -1) return false;
-    // the group units clear a new partial's captures to 0, which is the null
-    // of every type but STRING (dictionary id -1, cep.h): a STRING capture of
-    // a state a match may skip stays on the stand-alone walk (cap_null)
-    const auto& cs = q.nstates[cp.state];
-    const int ccol = q.rec_cols_a[cp.word];
-    if (cs.min_count == 0 && ccol >= 0 && ccol < (int)app.inputs[cs.stream].attrs.size() &&
-        app.inputs[cs.stream].attrs[ccol].type == T_STRING)
-      return false;
-    carry(ccol);
-  }
-  for (auto& it : q.select)
-    if (!(it.src == SRC_KEY || (it.src >= SRC_CAP && it.src < SRC_CAP + (int)q.ncaps.size()))) return false;
-  return true;
-}
-
-int mq_index(std::vector<int>& v, int x) {
-  for (size_t i = 0; i < v.size(); ++i)
-    if (v[i] == x) return (int)i;
-  v.push_back(x);
-  return (int)v.size() - 1;
-}
-
-// Condition bit of `tl` on stream s in group g (added when new); -1: full.
-int mq_cond_bit(MqRT& g, int s, const TermList& tl, bool add) {
-  if (tl.n == 0) return kMqTrueBit;
-  for (int c = 0; c < g.ncond[s]; ++c)
-    if (same_terms(g.conds[s * kMqMaxCond + c].tl, tl)) return c;
-  if (g.ncond[s] >= kMqMaxCond) return -1;
-  if (!add) return g.ncond[s];
-  MqCond& mc = g.conds[s * kMqMaxCond + g.ncond[s]];
-  std::memset(&mc, 0, sizeof(mc));
-  mc.tl = tl;
-  return g.ncond[s]++;
-}
-
-// Prefetched columns of a group: the key first, then condition and carried
-// columns (k_mqpart loads each once per row).
-std::vector<int> mq_pref_cols(const MqRT& g) {
-  std::vector<int> v{g.key_col};
-  for (int c : g.cond_cols) mq_index(v, c);
-  for (int c : g.carry) mq_index(v, c);
-  return v;
-}
-
-// A shape class of one group's queries (walk unit kinds, kernels.h MqUnit).
-struct MqClassB {
-  int kind = MQU_SEQ;
-  std::string sig;
-  int key_col = -1, layout = -1;
-  int view = -1;
-  std::vector<int> qs;
-  std::vector<MqNeeds> nds;
-};
-
-// Shape signature: queries with equal signatures run as one walk unit
-// (sequence classes advance bit-parallel, aggregations share the decode).
-std::string mq_signature(const cep_app* a, const Query& q, const MqNeeds& nd, int* kind) {
-  const CompiledApp& app = a->app;
-  std::string sg = std::to_string(nd.key_col) + "/" + std::to_string(nd.layout) + "/" + std::to_string(q.view) + "|";
-  auto add = [&](int64_t v) { sg += std::to_string(v) + ","; };
-  const auto& od = app.outputs[app.output_index(q.out_stream)];
-  for (auto& at : od.attrs) add(at.type);
-  sg += "|";
-  for (auto& it : q.select) add(it.src >= SRC_REC && it.src < SRC_REC + (int)q.rec_cols_a.size()
-                                    ? 1000 + q.rec_cols_a[it.src - SRC_REC] : it.src);
-  sg += "|";
-  if (q.kind == Q_AGG) {
-    *kind = MQU_AGG;
-    add(q.in_stream);
-    for (auto& ag : q.aggs) {
-      add(ag.fn);
-      add(ag.word >= 0 ? q.rec_cols_a[ag.word] : -1);
-      add(ag.arg_type);
-      add(ag.out_type);
-    }
-    sg += "|";
-    add(q.having_item);
-    if (q.having_item >= 0) {
-      add(q.having_cop);
-      add(q.having_ctype);
-    }
-    return "A" + sg;
-  }
-  // sequences: bit-parallel when every state reads its own stream and counts
-  // "one" or "one or more" (optional states allowed)
-  bool bp = true;
-  const int n = (int)q.nstates.size();
-  for (int j = 0; j < n; ++j) {
-    const auto& st = q.nstates[j];
-    for (int k = 0; k < j; ++k) bp = bp && q.nstates[k].stream != st.stream;
-    bp = bp && st.min_count <= 1 && (st.max_count == 1 || st.max_count < 0);
-  }
-  *kind = bp ? MQU_SEQ_BP : MQU_SEQ;
-  add(q.every ? 1 : 0);
-  add(q.within);
-  for (auto& st : q.nstates) {
-    add(st.stream);
-    add(st.min_count);
-    add(st.max_count);
-  }
-  sg += "|";
-  for (auto& cp : q.ncaps) {
-    add(cp.state);
-    add(cp.index);
-    add(q.rec_cols_a[cp.word]);
-  }
-  return "S" + sg;
-}
-
-// Record bit of a run of conditions on stream s (query order), sharing an
-// identical run already placed; -1 when the stream's bits are used up.
-int mq_cond_run(MqRT& g, int s, const std::vector<TermList>& run, bool add) {
-  const int n = (int)run.size();
-  for (int i = 0; i + n <= g.ncond[s]; ++i) {
-    bool same = true;
-    for (int j = 0; j < n && same; ++j) same = same_terms(g.conds[s * kMqMaxCond + i + j].tl, run[j]);
-    if (same) return i;
-  }
-  if (g.ncond[s] + n > kMqMaxCond) return -1;
-  if (!add) return g.ncond[s];
-  const int at = g.ncond[s];
-  for (int j = 0; j < n; ++j) {
-    MqCond& mc = g.conds[s * kMqMaxCond + at + j];
-    std::memset(&mc, 0, sizeof(mc));
-    mc.tl = run[j];
-  }
-  g.ncond[s] += n;
-  return at;
-}
-
-// Place a class's conditions into group g (bit-parallel classes: one run per
-// state; others: one bit per distinct condition).  false: no room.
-bool mq_place_conds(const cep_app* a, MqRT& g, const MqClassB& c) {
-  const CompiledApp& app = a->app;
-  if (c.kind == MQU_SEQ_BP) {
-    const Query& q0 = app.queries[c.qs[0]];
-    for (size_t j = 0; j < q0.nstates.size(); ++j) {
-      std::vector<TermList> run;
-      bool any = false;
-      for (int qi : c.qs) {
-        run.push_back(app.queries[qi].nstates[j].terms);
-        any = any || app.queries[qi].nstates[j].terms.n > 0;
-      }
-      if (any && mq_cond_run(g, q0.nstates[j].stream, run, true) < 0) return false;
-    }
-    return true;
-  }
-  for (auto& nd : c.nds)
-    for (auto& cd : nd.conds)
-      if (cd.second.n > 0 && mq_cond_run(g, cd.first, {cd.second}, true) < 0) return false;
-  return true;
-}
-
-int build_mq_groups(cep_app* a) {
-  const CompiledApp& app = a->app;
-  a->in_mq.assign(app.queries.size(), 0);
-  if (std::getenv("CEP_NO_MQ") || app.inputs.size() > 8) return CEP_OK;
-  // shape classes of the candidates, in plan order of their first query
-  std::vector<MqClassB> classes;
-  for (size_t qi = 0; qi < app.queries.size(); ++qi) {
-    MqNeeds nd;
-    if (!mq_candidate(a, app.queries[qi], &nd)) continue;
-    int kind;
-    const std::string sig = mq_signature(a, app.queries[qi], nd, &kind);
-    MqClassB* c = nullptr;
-    for (auto& x : classes)
-      if (x.sig == sig && x.kind != MQU_SEQ && (int)x.qs.size() < (x.kind == MQU_SEQ_BP ? kMqMaxCond : kMqMaxQ))
-        c = &x;
-    if (!c) {
-      classes.push_back(MqClassB());
-      c = &classes.back();
-      c->kind = kind;
-      c->sig = sig;
-      c->key_col = nd.key_col;
-      c->layout = nd.layout;
-      c->view = app.queries[qi].view;
-    }
-    c->qs.push_back((int)qi);
-    c->nds.push_back(nd);
-  }
-  // classes into groups: a class joins the first group with room (queries,
-  // carried / prefetched columns, condition bits); a class too large for an
-  // empty group is halved
-  std::vector<int> layouts;   // per group: a stream of its layout
-  std::vector<std::vector<MqClassB>> gclasses;
-  for (size_t ci = 0; ci < classes.size(); ++ci) {
-    MqClassB c = classes[ci];
-    auto fits = [&](MqRT& g) {
-      MqRT t;
-      t.key_col = g.key_col;
-      t.cond_cols = g.cond_cols;
-      t.carry = g.carry;
-      t.conds = g.conds;
-      std::copy(g.ncond, g.ncond + 8, t.ncond);
-      for (auto& nd : c.nds) {
-        for (int x : nd.cols) mq_index(t.cond_cols, x);
-        for (int x : nd.carry) mq_index(t.carry, x);
-      }
-      if ((int)t.carry.size() > kMqMaxCarry || (int)mq_pref_cols(t).size() > kPref) return false;
-      if ((int)(g.qs.size() + c.qs.size()) > kMqMaxQ) return false;
-      if (!mq_place_conds(a, t, c)) return false;
-      g.cond_cols = t.cond_cols;
-      g.carry = t.carry;
-      g.conds = t.conds;
-      std::copy(t.ncond, t.ncond + 8, g.ncond);
-      return true;
-    };
-    int gi = -1;
-    for (size_t i = 0; i < a->mqs.size() && gi < 0; ++i)
-      if (a->mqs[i].key_col == c.key_col && a->mqs[i].view == c.view && same_layout(app, layouts[i], c.layout) &&
-          fits(a->mqs[i]))
-        gi = (int)i;
-    if (gi < 0) {
-      MqRT g;
-      g.key_col = c.key_col;
-      g.view = c.view;
-      g.conds.resize(8 * kMqMaxCond);
-      if (!fits(g)) {
-        if (c.qs.size() > 1) {   // halve the class and place both halves
-          MqClassB h = c;
-          const size_t m = c.qs.size() / 2;
-          c.qs.resize(m);
-          c.nds.resize(m);
-          h.qs.erase(h.qs.begin(), h.qs.begin() + m);
-          h.nds.erase(h.nds.begin(), h.nds.begin() + m);
-          classes[ci] = c;
-          classes.insert(classes.begin() + ci + 1, h);
-          --ci;
-        }
-        continue;   // a single query that fits no group: general path
-      }
-      a->mqs.push_back(std::move(g));
-      layouts.push_back(c.layout);
-      gclasses.emplace_back();
-      gi = (int)a->mqs.size() - 1;
-    }
-    MqRT& g = a->mqs[gi];
-    for (int qi : c.qs) {
-      g.qs.push_back(qi);
-      a->in_mq[qi] = 1;
-    }
-    gclasses[gi].push_back(c);
-  }
-  // a group of one query stays on its own PatternRT: the key shuffle entry
-  // points (cep_route_batch / cep_send_records) and v2-v4 snapshots of such
-  // apps address that runtime
-  for (size_t gi = a->mqs.size(); gi-- > 0;) {
-    if (a->mqs[gi].qs.size() >= 2) continue;
-    for (int qi : a->mqs[gi].qs) a->in_mq[qi] = 0;
-    a->mqs.erase(a->mqs.begin() + gi);
-    gclasses.erase(gclasses.begin() + gi);
-    layouts.erase(layouts.begin() + gi);
-  }
-  for (size_t gi = 0; gi < a->mqs.size(); ++gi)
-    for (auto& c : gclasses[gi]) {
-      a->mqs[gi].classes_kind.push_back(c.kind);
-      a->mqs[gi].classes_n.push_back((int)c.qs.size());
-    }
-  // device descriptors, state and arenas per group
-  for (auto& g : a->mqs) {
-    const int64_t K = a->opt.key_capacity;
-    g.key_capacity = K;
-    g.key_stride = std::max(1, a->opt.key_stride);
-    g.key_offset = a->opt.key_offset;
-    int64_t chunk = std::max<int64_t>(a->opt.chunk_events, kMqTile);
-    chunk = std::min<int64_t>(chunk, (int64_t)kMqMaxTiles * kMqTile);
-    g.chunk = (chunk / kMqTile) * kMqTile;
-    const int nphys_max = std::min<int>((int)g.carry.size(), kMqMaxPhys);
-    const int W = mq_window(nphys_max);
-    // keys per bucket: about half a window of records per bucket per chunk
-    int64_t kpb = 64;
-    while (kpb * 2 <= kMqMaxKpb && (double)g.chunk * (double)(kpb * 2) / (double)K <= W / 2) kpb *= 2;
-    int lg = 0;
-    while (((K + (1 << lg) - 1) >> lg) > kpb) ++lg;
-    while (lg > 0 && (1 << lg) > kMqMaxBuckets) --lg;
-    kpb = (K + (1 << lg) - 1) >> lg;
-    if (kpb > kMqMaxKpb) return fail(a, CEP_E_CAPACITY, "key_capacity too large for a multi-query group");
-    g.lg = lg;
-    g.kpb = (int)kpb;
-    g.kstride = kpb << lg;
-    // descriptors (class order), then the walk units
-    int64_t off = 0;
-    std::vector<int> qkind;   // per descriptor: its class's unit kind
-    for (size_t ci = 0; ci < g.classes_kind.size(); ++ci)
-      for (int i = 0; i < g.classes_n[ci]; ++i) qkind.push_back(g.classes_kind[ci]);
-    for (int qi : g.qs) {
-      const Query& q = app.queries[qi];
-      MqQuery d;
-      std::memset(&d, 0, sizeof(d));
-      d.st_off = off;
-      const int oi = app.output_index(q.out_stream);
-      const auto& od = app.outputs[oi];
-      d.nsel = (int)q.select.size();
-      for (int i = 0; i < d.nsel; ++i) d.sel_type[i] = od.attrs[i].type;
-      d.hav_item = -1;
-      auto lword = [&](int col) { return col == g.key_col ? (int)MQ_SRC_KEY : mq_index(g.carry, col); };
-      if (q.kind == Q_AGG) {
-        d.kind = MQ_AGG;
-        d.in_stream = q.in_stream;
-        d.stream_mask = 1u << q.in_stream;
-        TermList f;
-        f.n = 0;
-        if (q.f.valid()) f = q.f_terms;
-        d.filter_bit = mq_cond_bit(g, q.in_stream, f, false);
-        d.nagg = (int)q.aggs.size();
-        for (int i = 0; i < d.nagg; ++i) {
-          d.agg_fn[i] = q.aggs[i].fn;
-          d.agg_arg_type[i] = q.aggs[i].arg_type;
-          d.agg_out_type[i] = q.aggs[i].out_type;
-          d.agg_src[i] = q.aggs[i].word >= 0 ? lword(q.rec_cols_a[q.aggs[i].word]) : (int)MQ_SRC_KEY;
-        }
-        for (int i = 0; i < d.nsel; ++i) {
-          const int src = q.select[i].src;
-          d.sel_src[i] = (src >= SRC_REC && src < SRC_REC + (int)q.rec_cols_a.size())
-                             ? SRC_REC + lword(q.rec_cols_a[src - SRC_REC])
-                             : src;
-        }
-        if (q.having_item >= 0) {
-          d.hav_item = q.having_item;
-          d.hav_cop = q.having_cop;
-          d.hav_ctype = q.having_ctype;
-          d.hav_cconst = q.having_cconst;
-        }
-        d.nwords = 1 + d.nagg;
-      } else {
-        d.kind = MQ_SEQ;
-        d.nstates = (int)q.nstates.size();
-        d.every = q.every ? 1 : 0;
-        d.within = q.within;
-        for (int j = 0; j < d.nstates; ++j) {
-          const auto& st = q.nstates[j];
-          d.stream_mask |= 1u << st.stream;
-          d.st_stream |= (uint32_t)st.stream << (3 * j);
-          d.st_bit |= (uint64_t)mq_cond_bit(g, st.stream, st.terms, false) << (6 * j);
-          d.st_min |= (uint64_t)st.min_count << (8 * j);
-          d.st_max |= (uint64_t)(st.max_count < 0 ? 0xff : st.max_count) << (8 * j);
-          bool opt = true;
-          for (int k = j + 1; k < d.nstates; ++k) opt = opt && q.nstates[k].min_count == 0;
-          if (opt) d.tail_opt |= 1u << j;
-        }
-        d.ncap = (int)q.ncaps.size();
-        for (int i = 0; i < d.ncap; ++i) {
-          d.cap_state[i] = q.ncaps[i].state;
-          d.cap_last[i] = q.ncaps[i].index < 0 ? 1 : 0;
-          d.cap_src[i] = lword(q.rec_cols_a[q.ncaps[i].word]);
-        }
-        for (int i = 0; i < d.nsel; ++i) d.sel_src[i] = q.select[i].src;
-        d.nwords = 2 + d.ncap;
-      }
-      for (int i = 0; i < d.nsel; ++i) {
-        const int src = d.sel_src[i];
-        d.sel_vi[i] = (src >= SRC_CAP && src < SRC_CAP + kMqMaxCaps) ? 1 + (src - SRC_CAP)
-                      : (src >= SRC_AGG && src < SRC_AGG + kMqMaxAggs) ? 1 + (src - SRC_AGG)
-                      : (src >= SRC_REC && src < SRC_REC + kMqMaxCarry) ? 5 + (src - SRC_REC)
-                                                                         : 0;
-        d.sel_w[i] = type_width(d.sel_type[i]);
-      }
-      d.hav_vi = d.hav_item >= 0 ? d.sel_vi[d.hav_item] : 0;
-      g.stream_mask |= d.stream_mask;
-      g.check_order = g.check_order || (d.kind == MQ_SEQ && d.within >= 0);
-      if (qkind[g.hq.size()] == MQU_SEQ_BP) d.nwords = 0;   // class state (unit)
-      off += d.nwords;
-      g.hq.push_back(d);
-    }
-    g.units.clear();
-    for (size_t ci = 0, q0 = 0; ci < g.classes_kind.size(); q0 += g.classes_n[ci], ++ci) {
-      const int n = g.classes_n[ci];
-      MqUnit u;
-      std::memset(&u, 0, sizeof(u));
-      u.kind = g.classes_kind[ci];
-      u.q0 = (int)q0;
-      if (u.kind == MQU_SEQ) {
-        for (int i = 0; i < n; ++i) {
-          u.q0 = (int)q0 + i;
-          u.nq = 1;
-          g.units.push_back(u);
-        }
-      } else if (u.kind == MQU_SEQ_BP) {
-        const Query& q = app.queries[g.qs[q0]];
-        const int N = (int)q.nstates.size();
-        u.nq = n;
-        u.st_off = off;
-        off += 4 + (int64_t)q.ncaps.size();   // live mask, started mask, state, start ts, captures
-        u.keep_last = q.nstates[N - 1].max_count < 0 ? 1 : 0;
-        for (int j = 0; j < N; ++j) {
-          const auto& st = q.nstates[j];
-          u.st_of_stream |= (uint32_t)(j + 1) << (4 * st.stream);
-          for (int t = 0; t < N; ++t) {
-            bool ok = (t == j && st.max_count < 0);
-            if (t > j) {
-              ok = true;
-              for (int k = j + 1; k < t; ++k) ok = ok && q.nstates[k].min_count == 0;
-            }
-            if (ok) u.allow |= 1ull << (j * 8 + t);
-          }
-          std::vector<TermList> run;
-          bool any = false;
-          for (int i = 0; i < n; ++i) {
-            run.push_back(app.queries[g.qs[q0 + i]].nstates[j].terms);
-            any = any || run.back().n > 0;
-          }
-          const uint64_t cb = any ? (uint64_t)mq_cond_run(g, st.stream, run, false) : 0xffull;
-          u.cbase |= cb << (8 * j);
-        }
-        for (int j = N; j < 8; ++j) u.cbase |= 0xffull << (8 * j);
-        g.units.push_back(u);
-      } else {
-        const Query& q = app.queries[g.qs[q0]];
-        int na = 0;
-        for (auto& ag : q.aggs) na += ag.fn != AGG_COUNT ? 1 : 0;
-        int nu = na <= 1 ? 8 : na == 2 ? 4 : 2;   // k_mqwalk's mq_agg_unit widths
-        static const int nu_cap = std::getenv("CEP_MQ_NU") ? std::atoi(std::getenv("CEP_MQ_NU")) : 8;
-        if (nu_cap == 4 || nu_cap == 2) nu = std::min(nu, nu_cap);   // diagnostics: narrower units
-        // mq_agg_fast: at most one non-count accumulator, having compared as
-        // a double or an integer (not a float)
-        const MqQuery& d0 = g.hq[q0];
-        int fast = 0;
-        if (na <= 1 && (d0.hav_item < 0 || d0.hav_ctype == T_DOUBLE || d0.hav_ctype == T_LONG ||
-                        d0.hav_ctype == T_INT)) {
-          fast = 9;
-          for (int y = 0; y < d0.nagg; ++y) {
-            const int fn = d0.agg_fn[y], t = d0.agg_arg_type[y];
-            if (fn == AGG_COUNT) continue;
-            const int acmp = (t == T_LONG || t == T_INT) ? 0 : t == T_FLOAT ? 1 : 2;
-            (void)acmp;   // min / max: generic mq_agg_unit (fast shapes 3-8 are not built)
-            fast = (fn == AGG_MIN || fn == AGG_MAX) ? 0 : (fn == AGG_SUM && d0.agg_out_type[y] == T_LONG) ? 2 : 1;
-          }
-        }
-        static const bool no_fast = std::getenv("CEP_MQ_GENERIC") != nullptr;   // diagnostics
-        if (fast && !no_fast) nu = std::min(nu, 4);   // mq_agg_fast is built 4 queries wide
-        for (int i = 0; i < n; i += nu) {
-          u.q0 = (int)q0 + i;
-          u.nq = std::min(nu, n - i);
-          u.nu = nu;
-          u.fast = no_fast ? 0 : fast;
-          g.units.push_back(u);
-        }
-      }
-    }
-    g.words = off;
-    const int ntiles = (int)(g.chunk / kMqTile);
-    bool ok = dev_ensure(&g.dq, g.hq.size() * sizeof(MqQuery), a->stream, false) &&
-              dev_ensure(&g.du, g.units.size() * sizeof(MqUnit), a->stream, false) &&
-              dev_ensure(&g.dconds, g.conds.size() * sizeof(MqCond), a->stream, false) &&
-              dev_ensure(&g.state, (size_t)g.words * g.kstride * 8, a->stream, false);
-    for (int b = 0; b < 2 && ok; ++b)
-      ok = dev_ensure(&g.recs[b], (size_t)g.chunk * (2 + nphys_max) * 8 + 16, a->stream, false) &&
-           dev_ensure(&g.toff[b], (size_t)((1 << lg) + 1) * ntiles * 2 + 16, a->stream, false) &&
-           dev_ensure(&g.chunk_base[b], 64, a->stream, false) &&
-           hipEventCreateWithFlags(&g.part_done[b], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&g.walk_done[b], hipEventDisableTiming) == hipSuccess;
-    if (!ok) return fail(a, CEP_E_DEVICE, "out of device memory (multi-query group)");
-    hipMemset(g.state.p, 0, (size_t)g.words * g.kstride * 8);
-    // condition slots: the prefetch slot of each term's column
-    const std::vector<int> pc = mq_pref_cols(g);
-    for (auto& mc : g.conds)
-      for (int i = 0; i < mc.tl.n && i < kMaxTerms; ++i)
-        for (size_t sl = 0; sl < pc.size(); ++sl)
-          if (pc[sl] == mc.tl.t[i].col) mc.slot[i] = (int32_t)sl;
-    hipMemcpy(g.dconds.p, g.conds.data(), g.conds.size() * sizeof(MqCond), hipMemcpyHostToDevice);
-    hipMemcpy(g.du.p, g.units.data(), g.units.size() * sizeof(MqUnit), hipMemcpyHostToDevice);
-  }
-  return CEP_OK;
-}
 
 int create_runtime(cep_app* a) {
   const CompiledApp& app = a->app;
@@ -993,15 +121,9 @@ int create_runtime(cep_app* a) {
   if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
     return fail(a, CEP_E_DEVICE, std::string("libcep is built for gfx950, device is ") +
                                      prop.gcnArchName);
-  if (hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&a->side, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&a->in_ready, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&a->ext_ready, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&a->out_ready, hipEventDisableTiming) != hipSuccess ||
-      hipStreamCreateWithFlags(&a->copy, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&a->rstream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&a->r_ready, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&a->r_host, hipEventDisableTiming) != hipSuccess)
+  if (!a->stream.create() || !a->side.create() || !a->in_ready.create() || !a->ext_ready.create() ||
+      !a->out_ready.create() || !a->copy.create() || !a->rstream.create() || !a->r_ready.create() ||
+      !a->r_host.create())
     return fail(a, CEP_E_DEVICE, "hipStreamCreate failed");
   size_t cb = std::max<size_t>(app.code.size(), 1) * sizeof(Ins);
   size_t kb = std::max<size_t>(app.konst.size(), 1) * 8;
@@ -1193,13 +315,13 @@ int create_runtime(cep_app* a) {
                                            (q.win_kind == WIN_TIME ? " or pending_slots" : ""));
     }
     if (!dev_ensure(&rt.khdr, (size_t)rt.kstride * 4, a->stream, false) ||
-        !dev_ensure(&rt.kslot, (size_t)rt.kstride * bank * S * p.slot_words * 8, a->stream, false) ||
-        !dev_ensure(&rt.chunk_base[0], 64, a->stream, false) ||
-        !dev_ensure(&rt.chunk_base[1], 64, a->stream, false))
+        !dev_ensure(&rt.kslot, (size_t)rt.kstride * bank * S * p.slot_words * 8, a->stream, false))
       return fail(a, CEP_E_DEVICE, "out of device memory (pattern state)");
     hipMemset(rt.khdr.p, 0, (size_t)rt.kstride * 4);
-    // (snapshots store a live key's whole slot: free ring entries read as zero)
-    if (win) hipMemset(rt.kslot.p, 0, (size_t)rt.kstride * bank * S * p.slot_words * 8);
+    // snapshots store a live key's whole slots: a window's free ring entries,
+    // and slot word 1, which the closed form never writes, read as zero
+    // instead of whatever the memory held before
+    hipMemset(rt.kslot.p, 0, (size_t)rt.kstride * bank * S * p.slot_words * 8);
     // the walk build decides the chunk cap (its LDS segment tables)
     bool walk_vm = q.g_in_walk || agg || q.nfa;
     for (auto& it : q.select) walk_vm |= it.src == SRC_VM;
@@ -1208,7 +330,7 @@ int create_runtime(cep_app* a) {
     chunk = std::min<int64_t>(chunk, (int64_t)(walk_vm ? kWalkMaxTiles : kWalkMaxTiles / 4) *
                                          kPartThreads * kPartItems);
     chunk = (chunk / (kPartThreads * kPartItems)) * (kPartThreads * kPartItems);
-    rt.chunk = chunk;
+    rt.pipe.chunk = chunk;
     // the order-tolerant form of a `within` pattern (ts_order 0, released
     // late rows) runs on the VM walk, whose segment tables hold 4x the tiles:
     // its chunks may be that long, so per-key state is loaded and committed
@@ -1221,14 +343,9 @@ int create_runtime(cep_app* a) {
     }
     rt.chunk_tol = chunk_tol;
     const int64_t ntiles = std::max(chunk, chunk_tol) / (kPartThreads * kPartItems);
-    for (int b = 0; b < 2; ++b) {
-      if (!dev_ensure(&rt.recs[b], (size_t)std::max(chunk, chunk_tol) * p.rec_words * 8 + 16, a->stream, false) ||
-          !dev_ensure(&rt.tile_off[b], (size_t)ntiles * ((1 << lg) + 1) * 2, a->stream, false))
-        return fail(a, CEP_E_DEVICE, "out of device memory (record arena)");
-      if (hipEventCreateWithFlags(&rt.part_done[b], hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&rt.walk_done[b], hipEventDisableTiming) != hipSuccess)
-        return fail(a, CEP_E_DEVICE, "hipEventCreate failed");
-    }
+    if (!rt.pipe.alloc((size_t)std::max(chunk, chunk_tol) * p.rec_words * 8 + 16,
+                       (size_t)ntiles * ((1 << lg) + 1) * 2, a->stream))
+      return fail(a, CEP_E_DEVICE, "out of device memory (record arena)");
     rt.extra_bound = (int64_t)S * kc;
     rt.part_vm = (q.f.off >= 0 && q.f_terms.n < 0) || (q.g_raw.off >= 0 && q.g_terms.n < 0) || q.nfa;
     // fast partition path: all columns the pass reads fit kPref registers
@@ -1271,6 +388,7 @@ int create_runtime(cep_app* a) {
                       dev_ensure(&rt.pool_cur, 64, a->stream, false);
       if (!ok) return fail(a, CEP_E_DEVICE, "out of device memory (pending pool)");
       hipMemset(rt.kext.p, 0, (size_t)rt.kstride * 8);
+      for (auto& pl : rt.pool) hipMemset(pl.p, 0, (size_t)rt.pool_cap * p.slot_words * 8);   // (as kslot)
       rt.extra_bound += rt.pool_cap;   // pool partials may complete too
     }
     // closed-form fast path: `every A -> B` with f / g as term lists on the
@@ -1314,6 +432,7 @@ int create_runtime(cep_app* a) {
              dev_ensure(&rt.pool_cur, 64, a->stream, false);
         if (!ok) return fail(a, CEP_E_DEVICE, "out of device memory (pending pool)");
         hipMemset(rt.kext.p, 0, (size_t)rt.kstride * 8);
+        for (auto& pl : rt.pool) hipMemset(pl.p, 0, (size_t)rt.pool_cap * p.slot_words * 8);   // (as kslot)
         if (!pool_counted) rt.extra_bound += rt.pool_cap;   // pool partials may complete too
         rt.cf = true;
         rt.cf_chunk = cc;
@@ -1327,8 +446,7 @@ int create_runtime(cep_app* a) {
                dev_ensure(&rt.cand, kCfHotMax * 4 * 8, a->stream, false) &&
                dev_ensure(&rt.ncand, 64, a->stream, false) && dev_ensure(&rt.hot_active, 64, a->stream, false) &&
                host_ensure(&rt.hot_active_host, 64);
-          ok = ok && hipEventCreateWithFlags(&rt.hot_fork, hipEventDisableTiming) == hipSuccess &&
-               hipEventCreateWithFlags(&rt.hot_join, hipEventDisableTiming) == hipSuccess;
+          ok = ok && rt.hot_fork.create() && rt.hot_join.create();
           if (!ok) return fail(a, CEP_E_DEVICE, "out of device memory (hot keys)");
           hipMemset(rt.hot_id.p, 0xff, (size_t)kc * 2 + 16);
           hipMemset(rt.hot_key.p, 0xff, kCfHotMax * 4);
@@ -1371,7 +489,7 @@ int create_runtime(cep_app* a) {
     // every row of its streams and prunes by |ts - ts(s1)| in any order, an
     // aggregation has no window: neither needs the re-run
     rt.order_sensitive = p.within >= 0 && !agg && !(q.nfa && q.sequence);
-    a->pats.push_back(rt);
+    a->pats.push_back(std::move(rt));
   }
   for (size_t qi = 0; qi < app.queries.size(); ++qi) {
     const Query& q = app.queries[qi];
@@ -1429,7 +547,7 @@ int create_runtime(cep_app* a) {
     }
     if (!ok) return fail(a, CEP_E_DEVICE, "out of device memory (join state)");
     hipMemset(rt.st.p, 0, sizeof(JoinState));
-    a->joins.push_back(rt);
+    a->joins.push_back(std::move(rt));
   }
   // event tables: per table one pipeline over all its operations
   if (!app.tables.empty()) {
@@ -1508,20 +626,15 @@ int create_runtime(cep_app* a) {
     int64_t chunk = std::max<int64_t>(a->opt.chunk_events, kPartThreads * kPartItems);
     chunk = std::min<int64_t>(chunk, (int64_t)kWalkMaxTiles * kPartThreads * kPartItems);
     chunk = (chunk / (kPartThreads * kPartItems)) * (kPartThreads * kPartItems);
-    rt.chunk = chunk;
+    rt.pipe.chunk = chunk;
     const int64_t ntiles = chunk / (kPartThreads * kPartItems);
-    bool ok = dev_ensure(&rt.thdr, (size_t)rt.kstride * 4, a->stream, false) &&
-              dev_ensure(&rt.tword, (size_t)rt.kstride * ta.nwords * 8, a->stream, false);
-    for (int b = 0; b < 2 && ok; ++b)
-      ok = dev_ensure(&rt.recs[b], (size_t)chunk * p.rec_words * 8 + 16, a->stream, false) &&
-           dev_ensure(&rt.tile_off[b], (size_t)ntiles * ((1 << lg) + 1) * 2, a->stream, false) &&
-           dev_ensure(&rt.chunk_base[b], 64, a->stream, false) &&
-           hipEventCreateWithFlags(&rt.part_done[b], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&rt.walk_done[b], hipEventDisableTiming) == hipSuccess;
+    const bool ok = dev_ensure(&rt.thdr, (size_t)rt.kstride * 4, a->stream, false) &&
+                    dev_ensure(&rt.tword, (size_t)rt.kstride * ta.nwords * 8, a->stream, false) &&
+                    rt.pipe.alloc((size_t)chunk * p.rec_words * 8 + 16, (size_t)ntiles * ((1 << lg) + 1) * 2, a->stream);
     if (!ok) return fail(a, CEP_E_DEVICE, "out of device memory (table " + T.schema.id + ")");
     hipMemset(rt.thdr.p, 0, (size_t)rt.kstride * 4);
     hipMemset(rt.tword.p, 0, (size_t)rt.kstride * ta.nwords * 8);
-    a->tabs.push_back(rt);
+    a->tabs.push_back(std::move(rt));
   }
   {
     const int64_t none = INT64_MIN;
@@ -1720,18 +833,9 @@ int run_pattern_cf(cep_app* a, PatternRT& rt, const Query& q, OutStream& o,
                    const uint64_t* in_recs = nullptr, int in_rec_words = 0, bool tol = false) {
   const int P = 1 << rt.pa.buckets_log2;
   const bool hot_ok = rt.hot;
-  // Both passes on the main stream by default: k_cfpart and k_cfwalk cannot
-  // share a CU (each fills its register file), so the side stream only
-  // time-slices them (measured: no throughput gain, inflated kernel times).
-  // CEP_OVERLAP=1 puts the partition on the side stream.  Serial mode issues
-  // no cross-stream events: every event between two kernels of one stream
-  // costs a gap (rocprofv3 trace: ~15 us between k_cfpart and k_cfwalk).
-  static const bool overlap = std::getenv("CEP_OVERLAP") != nullptr;
-  hipStream_t side = overlap ? a->side : a->stream;
-  if (overlap) {
-    hipEventRecord(a->in_ready, a->stream);
-    hipStreamWaitEvent(a->side, a->in_ready, 0);
-  }
+  ChunkPipe& pipe = rt.pipe;   // (its events, chunk_base and parity; the arenas are cf_recs / cf_toff)
+  hipStream_t side = pipe.open_cf(a);
+  const bool overlap = pipe.events;   // CEP_OVERLAP=1
   // Hot-key probe: until diversion has been decided once, the first chunk is
   // short (kHotProbeRows) and followed by one stream sync, so a skewed
   // stream's hottest keys are diverted from the second chunk on instead of
@@ -1740,8 +844,7 @@ int run_pattern_cf(cep_app* a, PatternRT& rt, const Query& q, OutStream& o,
   // runtime.
   constexpr int64_t kHotProbeRows = 1 << 20;
   for (int64_t r0 = 0, step = 0; r0 < rows_all.n; r0 += step) {
-    const int b = rt.cur;
-    rt.cur ^= 1;
+    const int b = pipe.begin(side);
     const bool probe = hot_ok && !rt.hot_on && !rt.hot_probed;
     step = std::min<int64_t>(probe ? std::min<int64_t>(kHotProbeRows, rt.cf_chunk) : rt.cf_chunk, rows_all.n - r0);
     RowsArgs rows = rows_all;
@@ -1762,7 +865,7 @@ int run_pattern_cf(cep_app* a, PatternRT& rt, const Query& q, OutStream& o,
     pa.pat.tolerant = tol ? 1 : 0;
     pa.cf = cf;
     cf_drop_ts_slot(&pa);
-    pa.chunk_base = (int64_t*)rt.chunk_base[b].p;
+    pa.chunk_base = (int64_t*)pipe.chunk_base[b].p;
     pa.recs = (uint64_t*)rt.cf_recs[b].p;
     pa.tile_off = (uint16_t*)rt.cf_toff[b].p;
     pa.ntiles = (int32_t)ntiles;
@@ -1828,11 +931,10 @@ int run_pattern_cf(cep_app* a, PatternRT& rt, const Query& q, OutStream& o,
       pa.gate = (uint32_t*)rt.atol_gate.p;
       pa.gate_seq = gseq;
     }
-    if (overlap && rt.used[b]) hipStreamWaitEvent(side, rt.walk_done[b], 0);   // arena b is free
     // hot keys: k_cfpart reads hot_id, which the previous chunk's
     // k_hot_update rewrites on the main stream (walk_done is recorded after
     // it), so with diversion candidates the partition waits for that chunk
-    if (overlap && hot && rt.used[b ^ 1]) hipStreamWaitEvent(side, rt.walk_done[b ^ 1], 0);
+    if (overlap && hot && pipe.used[b ^ 1]) hipStreamWaitEvent(side, pipe.walk_done[b ^ 1], 0);
     if (atol) {
       CfPartArgs aa = pa;
       aa.atol = 1;
@@ -1849,17 +951,14 @@ int run_pattern_cf(cep_app* a, PatternRT& rt, const Query& q, OutStream& o,
       if (cf_partition_2wg(pa)) a->launches[CEP_K_CF_PARTITION_2WG]++;   // (k_cfpart2: counted under both)
       launch_cf_partition(pa, ntiles, side);
     }
-    if (overlap) {
-      hipEventRecord(rt.part_done[b], side);
-      hipStreamWaitEvent(a->stream, rt.part_done[b], 0);
-    }
+    pipe.partitioned(b, side, a->stream);
     CfWalkArgs wa{};
     wa.pat = pa.pat;
     wa.cf = cf;
     wa.recs = pa.recs;
     wa.tile_off = pa.tile_off;
     wa.ntiles = (int32_t)ntiles;
-    wa.chunk_base = (const int64_t*)rt.chunk_base[b].p;
+    wa.chunk_base = (const int64_t*)pipe.chunk_base[b].p;
     wa.khdr = (uint32_t*)rt.khdr.p;
     wa.kslot = (uint64_t*)rt.kslot.p;
     wa.kstride = rt.kstride;
@@ -1878,7 +977,7 @@ int run_pattern_cf(cep_app* a, PatternRT& rt, const Query& q, OutStream& o,
       ha.recs = pa.recs;
       ha.tile_off = pa.tile_off;
       ha.ntiles = (int32_t)ntiles;
-      ha.chunk_base = (const int64_t*)rt.chunk_base[b].p;
+      ha.chunk_base = (const int64_t*)pipe.chunk_base[b].p;
       ha.hot_id = (uint16_t*)rt.hot_id.p;
       ha.hot_key = (int32_t*)rt.hot_key.p;
       ha.hot_m = (uint32_t*)rt.hot_m.p;
@@ -1979,8 +1078,7 @@ int run_pattern_cf(cep_app* a, PatternRT& rt, const Query& q, OutStream& o,
       }
     }
     rt.pool_side ^= 1;   // this launch's write pool holds every run now
-    if (overlap) hipEventRecord(rt.walk_done[b], a->stream);
-    rt.used[b] = true;
+    pipe.walked(b, a->stream);
   }
   return CEP_OK;
 }
@@ -2025,8 +1123,8 @@ PatternArgs tolerant_args(const PatternRT& rt, const Query& q) {
 
 // tolerant: run on the order-tolerant path (rows whose ts may go backwards:
 // a watermark release holding late rows, or the re-run after a descent).
-int run_pattern(cep_app* a, PatternRT& rt, const RowsArgs& rows_in,
-                const uint64_t* in_recs = nullptr, int in_rec_words = 0, bool tolerant = false) {
+int run_pattern(cep_app* a, PatternRT& rt, const RowsArgs& rows_in, const uint64_t* in_recs, int in_rec_words,
+                bool tolerant) {
   const Query& q = a->app.queries[rt.q];
   OutStream& o = a->outs[a->app.output_index(q.out_stream)];
   if (o.bound == 0) o.bound = rt.extra_bound;
@@ -2109,17 +1207,11 @@ int run_pattern(cep_app* a, PatternRT& rt, const RowsArgs& rows_in,
   }
   const int P = 1 << rt.pa.buckets_log2;
   rt.atol_ok = false;   // this path keeps no high-water mark: adaptive chunks off for good
-  // the side stream starts after everything already queued on the main stream
-  // (host-batch staging copies, earlier queries)
-  hipEventRecord(a->in_ready, a->stream);
-  hipStreamWaitEvent(a->side, a->in_ready, 0);
-  // CEP_NO_OVERLAP=1 (diagnostics): both passes on the main stream
-  static const bool no_overlap = std::getenv("CEP_NO_OVERLAP") != nullptr;
-  hipStream_t side = no_overlap ? a->stream : a->side;
-  const int64_t cstep = tolerant ? rt.chunk_tol : rt.chunk;
+  ChunkPipe& pipe = rt.pipe;
+  hipStream_t side = pipe.open(a);
+  const int64_t cstep = tolerant ? rt.chunk_tol : pipe.chunk;
   for (int64_t r0 = 0; r0 < rows_all.n; r0 += cstep) {
-    const int b = rt.cur;
-    rt.cur ^= 1;
+    const int b = pipe.begin(side);
     RowsArgs rows = rows_all;
     rows.row0 = rows_all.row0 + r0;
     rows.n = std::min<int64_t>(cstep, rows_all.n - r0);
@@ -2139,18 +1231,16 @@ int run_pattern(cep_app* a, PatternRT& rt, const RowsArgs& rows_in,
     pa.vm = {(const Ins*)a->code.p, (const uint64_t*)a->konst.p};
     pa.pat = tolerant ? tolerant_args(rt, q) : rt.pa;
     pa.tile_rows = kPartThreads * kPartItems;
-    pa.recs = (uint64_t*)rt.recs[b].p;
-    pa.tile_off = (uint16_t*)rt.tile_off[b].p;
-    pa.chunk_base = (int64_t*)rt.chunk_base[b].p;
+    pa.recs = (uint64_t*)pipe.recs[b].p;
+    pa.tile_off = (uint16_t*)pipe.tile_off[b].p;
+    pa.chunk_base = (int64_t*)pipe.chunk_base[b].p;
     pa.err = (unsigned int*)a->err.p;
     if (a->stamps.p) pa.stamps = (uint64_t*)a->stamps.p + 4096 * 16;
-    if (rt.used[b]) hipStreamWaitEvent(side, rt.walk_done[b], 0);   // arena b is free
     {
       LaunchTimer t(a, CEP_K_PARTITION, side);
       launch_partition(pa, ntiles, rt.part_vm, side);
     }
-    hipEventRecord(rt.part_done[b], side);
-    hipStreamWaitEvent(a->stream, rt.part_done[b], 0);
+    pipe.partitioned(b, side, a->stream);
     WalkArgs wa{};
     wa.vm = pa.vm;
     wa.pat = pa.pat;
@@ -2158,7 +1248,7 @@ int run_pattern(cep_app* a, PatternRT& rt, const RowsArgs& rows_in,
     wa.tile_off = pa.tile_off;
     wa.ntiles = (int)ntiles;
     wa.tile_rows = pa.tile_rows;
-    wa.chunk_base = (const int64_t*)rt.chunk_base[b].p;
+    wa.chunk_base = (const int64_t*)pipe.chunk_base[b].p;
     if (a->stamps.p) {
       // keep the last chunk's stamps (diagnostics only)
       wa.stamps = (uint64_t*)a->stamps.p;
@@ -2186,8 +1276,7 @@ int run_pattern(cep_app* a, PatternRT& rt, const RowsArgs& rows_in,
         LaunchTimer t(a, CEP_K_AGG);
         launch_winwalk(ww, P, rt.win_vm, a->stream);
       }
-      hipEventRecord(rt.walk_done[b], a->stream);
-      rt.used[b] = true;
+      pipe.walked(b, a->stream);
       continue;
     }
     const bool pool = (q.nfa || pa.pat.nfa_pair) && rt.kext.p;
@@ -2204,8 +1293,7 @@ int run_pattern(cep_app* a, PatternRT& rt, const RowsArgs& rows_in,
       launch_walk(wa, P, rt.walk_vm || pa.pat.nfa_pair, a->stream);
     }
     if (pool) rt.pool_side ^= 1;   // this launch's write pool holds every run now
-    hipEventRecord(rt.walk_done[b], a->stream);
-    rt.used[b] = true;
+    pipe.walked(b, a->stream);
   }
   return CEP_OK;
 }
@@ -2298,30 +1386,24 @@ int run_mq(cep_app* a, MqRT& g, const RowsArgs& rows_all) {
     wa.stamps = (uint64_t*)a->stamps.p;
     hipMemsetAsync(wa.stamps, 0, (size_t)(1 << g.lg) * 16 * 8, a->stream);
   }
-  // the side stream starts after everything already queued on the main one
-  hipEventRecord(a->in_ready, a->stream);
-  hipStreamWaitEvent(a->side, a->in_ready, 0);
-  static const bool no_overlap = std::getenv("CEP_NO_OVERLAP") != nullptr;
-  hipStream_t side = no_overlap ? a->stream : a->side;
-  for (int64_t r0 = 0; r0 < rows_all.n; r0 += g.chunk) {
-    const int b = g.cur;
-    g.cur ^= 1;
+  ChunkPipe& pipe = g.pipe;
+  hipStream_t side = pipe.open(a);
+  for (int64_t r0 = 0; r0 < rows_all.n; r0 += pipe.chunk) {
+    const int b = pipe.begin(side);
     RowsArgs rows = rows_all;
     rows.row0 = rows_all.row0 + r0;
-    rows.n = std::min<int64_t>(g.chunk, rows_all.n - r0);
+    rows.n = std::min<int64_t>(pipe.chunk, rows_all.n - r0);
     const int ntiles = (int)((rows.n + kMqTile - 1) / kMqTile);
     pa.rows = rows;
     pa.ntiles = ntiles;
-    pa.chunk_base = (int64_t*)g.chunk_base[b].p;
-    pa.recs = (uint64_t*)g.recs[b].p;
-    pa.tile_off = (uint16_t*)g.toff[b].p;
-    if (g.used[b]) hipStreamWaitEvent(side, g.walk_done[b], 0);   // arena b is free
+    pa.chunk_base = (int64_t*)pipe.chunk_base[b].p;
+    pa.recs = (uint64_t*)pipe.recs[b].p;
+    pa.tile_off = (uint16_t*)pipe.tile_off[b].p;
     {
       LaunchTimer t(a, CEP_K_MQ_PARTITION, side);
       launch_mq_partition(pa, side);
     }
-    hipEventRecord(g.part_done[b], side);
-    hipStreamWaitEvent(a->stream, g.part_done[b], 0);
+    pipe.partitioned(b, side, a->stream);
     wa.recs = pa.recs;
     wa.tile_off = pa.tile_off;
     wa.ntiles = ntiles;
@@ -2331,8 +1413,7 @@ int run_mq(cep_app* a, MqRT& g, const RowsArgs& rows_all) {
       LaunchTimer t(a, CEP_K_MQ_WALK);
       launch_mq_walk(wa, 1 << g.lg, a->stream);
     }
-    hipEventRecord(g.walk_done[b], a->stream);
-    g.used[b] = true;
+    pipe.walked(b, a->stream);
   }
   return CEP_OK;
 }
@@ -2535,16 +1616,13 @@ int run_table(cep_app* a, TableRT& rt, const RowsArgs& rows_all) {
     if (rc) return rc;
   }
   const int P = 1 << rt.pa.buckets_log2;
-  hipEventRecord(a->in_ready, a->stream);
-  hipStreamWaitEvent(a->side, a->in_ready, 0);
-  static const bool no_overlap = std::getenv("CEP_NO_OVERLAP") != nullptr;
-  hipStream_t side = no_overlap ? a->stream : a->side;
-  for (int64_t r0 = 0; r0 < rows_all.n; r0 += rt.chunk) {
-    const int b = rt.cur;
-    rt.cur ^= 1;
+  ChunkPipe& pipe = rt.pipe;
+  hipStream_t side = pipe.open(a);
+  for (int64_t r0 = 0; r0 < rows_all.n; r0 += pipe.chunk) {
+    const int b = pipe.begin(side);
     RowsArgs rows = rows_all;
     rows.row0 = rows_all.row0 + r0;
-    rows.n = std::min<int64_t>(rt.chunk, rows_all.n - r0);
+    rows.n = std::min<int64_t>(pipe.chunk, rows_all.n - r0);
     rows.prev_ts = INT64_MIN;   // timestamps play no part: no order check
     rows.prev_ts_dev = nullptr;
     const int64_t ntiles = (rows.n + kPartThreads * kPartItems - 1) / (kPartThreads * kPartItems);
@@ -2554,17 +1632,15 @@ int run_table(cep_app* a, TableRT& rt, const RowsArgs& rows_all) {
     pa.vm = {(const Ins*)a->code.p, (const uint64_t*)a->konst.p};
     pa.pat = rt.pa;
     pa.tile_rows = kPartThreads * kPartItems;
-    pa.recs = (uint64_t*)rt.recs[b].p;
-    pa.tile_off = (uint16_t*)rt.tile_off[b].p;
-    pa.chunk_base = (int64_t*)rt.chunk_base[b].p;
+    pa.recs = (uint64_t*)pipe.recs[b].p;
+    pa.tile_off = (uint16_t*)pipe.tile_off[b].p;
+    pa.chunk_base = (int64_t*)pipe.chunk_base[b].p;
     pa.err = (unsigned int*)a->err.p;
-    if (rt.used[b]) hipStreamWaitEvent(side, rt.walk_done[b], 0);   // arena b is free
     {
       LaunchTimer t(a, CEP_K_PARTITION, side);
       launch_partition(pa, ntiles, true, side);   // (the N-state record form is the interpreter build's)
     }
-    hipEventRecord(rt.part_done[b], side);
-    hipStreamWaitEvent(a->stream, rt.part_done[b], 0);
+    pipe.partitioned(b, side, a->stream);
     TabArgs ta = rt.ta;
     ta.vm = pa.vm;
     ta.pat = pa.pat;
@@ -2588,8 +1664,7 @@ int run_table(cep_app* a, TableRT& rt, const RowsArgs& rows_all) {
       if (rt.vm) a->tab_vm_launches++;
       launch_tabwalk(ta, P, rt.vm, a->stream);
     }
-    hipEventRecord(rt.walk_done[b], a->stream);
-    rt.used[b] = true;
+    pipe.walked(b, a->stream);
   }
   return CEP_OK;
 }
@@ -2697,7 +1772,7 @@ int error_status(cep_app* a, unsigned int e) {
   return fail(a, CEP_E_DEVICE, "device error flags " + std::to_string(e));
 }
 
-}  // namespace
+}  // namespace cep
 
 // ======================================================================= C ABI
 extern "C" {
@@ -2807,255 +1882,12 @@ extern "C" {
 
 void cep_destroy(cep_app* a) {
   if (!a) return;
-  if (a->stream) hipStreamSynchronize(a->stream);
-  if (a->stamps.p && !a->pats.empty()) {
-    // diagnostics: mean duration of each k_walk phase over the last launch's blocks
-    const int nb = 1 << a->pats[0].pa.buckets_log2;
-    std::vector<uint64_t> st((size_t)4096 * 16);
-    hipMemcpy(st.data(), a->stamps.p, st.size() * 8, hipMemcpyDeviceToHost);
-    // phases 1..7 of window 0, then phases 2..7 of window 1 (stamps 10..15,
-    // relative to window 0's last stamp); blocks with one window have zeros
-    double sum[16] = {0};
-    int n1 = 0;
-    for (int b = 0; b < nb; ++b) {
-      const uint64_t* t = &st[(size_t)b * 16];
-      for (int i = 1; i < 8; ++i)
-        if (t[i] && t[i - 1]) sum[i] += (double)(t[i] - t[i - 1]);
-      if (t[10] && t[7]) {
-        ++n1;
-        sum[10] += (double)(t[10] - t[7]);
-        for (int i = 11; i < 16; ++i)
-          if (t[i] && t[i - 1]) sum[i] += (double)(t[i] - t[i - 1]);
-      }
-    }
-    {   // slowest blocks (stragglers): first stamp to the last one written
-      std::vector<std::pair<uint64_t, int>> dur;
-      for (int b = 0; b < nb; ++b) {
-        const uint64_t* t = &st[(size_t)b * 16];
-        uint64_t hi = 0;
-        for (int i = 0; i < 16; ++i) hi = std::max(hi, t[i]);
-        if (t[0] && hi > t[0]) dur.push_back({hi - t[0], b});
-      }
-      std::sort(dur.rbegin(), dur.rend());
-      std::fprintf(stderr, "[cep stamps] slowest walk blocks (ticks):");
-      for (size_t i = 0; i < dur.size() && i < 6; ++i) std::fprintf(stderr, " b%d=%llu", dur[i].second,
-                                                                   (unsigned long long)dur[i].first);
-      if (!dur.empty()) std::fprintf(stderr, " median=%llu", (unsigned long long)dur[dur.size() / 2].first);
-      std::fprintf(stderr, "\n");
-    }
-    {   // every stamp against the previous one (both kernels' layouts)
-      double dsum[16] = {0};
-      int dn[16] = {0};
-      for (int b = 0; b < nb; ++b) {
-        const uint64_t* t = &st[(size_t)b * 16];
-        for (int i = 1; i < 16; ++i)
-          if (t[i] && t[i - 1]) {
-            dsum[i] += (double)(t[i] - t[i - 1]);
-            ++dn[i];
-          }
-      }
-      std::fprintf(stderr, "[cep stamps] walk deltas ticks/block:");
-      for (int i = 1; i < 16; ++i) std::fprintf(stderr, " d%d=%.0f(%d)", i, dn[i] ? dsum[i] / dn[i] : 0.0, dn[i]);
-      std::fprintf(stderr, "\n");
-    }
-    if (std::getenv("CEP_WAVESTAMP")) {   // -DCF_WAVESTAMP build: per-wave ends vs slot 0
-      double m[16] = {0};
-      int c[16] = {0};
-      for (int b = 0; b < nb; ++b) {
-        const uint64_t* t = &st[(size_t)b * 16];
-        if (!t[0]) continue;
-        for (int i = 1; i < 16; ++i)
-          if (t[i]) {
-            m[i] += (double)(int64_t)(t[i] - t[0]);
-            ++c[i];
-          }
-      }
-      std::fprintf(stderr, "[cep wavestamps] commit end per wave:");
-      for (int i = 1; i <= 8; ++i) std::fprintf(stderr, " w%d=%.0f", i - 1, c[i] ? m[i] / c[i] : 0.0);
-      std::fprintf(stderr, "\n[cep wavestamps] emission end per wave:");
-      for (int i = 9; i < 16; ++i) std::fprintf(stderr, " w%d=%.0f", i - 9, c[i] ? m[i] / c[i] : 0.0);
-      std::fprintf(stderr, "\n");
-    }
-    std::fprintf(stderr, "[cep stamps] walk window0 ticks/block:");
-    for (int i = 1; i < 8; ++i) std::fprintf(stderr, " p%d=%.0f", i, sum[i] / nb);
-    std::fprintf(stderr, "\n[cep stamps] walk window1 (%d blocks):", n1);
-    for (int i = 10; i < 16; ++i) std::fprintf(stderr, " p%d=%.0f", i - 8, n1 ? sum[i] / n1 : 0.0);
-    std::fprintf(stderr, "\n");
-    const uint64_t* c = &st[(size_t)4095 * 16];
-    if (nb <= 4095 && c[0] && !c[5 + 8])
-      std::fprintf(stderr, "[cep counters] walk2 active keys=%llu n>2=%llu n>4=%llu n>6=%llu n>8=%llu | waves: n>2=%llu n>4=%llu of %llu\n",
-                   (unsigned long long)c[0], (unsigned long long)c[1], (unsigned long long)c[2],
-                   (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[5],
-                   (unsigned long long)c[6], (unsigned long long)c[7]);
-    if (nb <= 4095 && (c[5] || c[7]))
-      std::fprintf(stderr, "[cep counters] walk: carried=%llu all=%llu keylanes_n>2=%llu drop_n>2=%llu "
-                   "slot_st>=2=%llu windows=%llu keylanes=%llu\n",
-                   (unsigned long long)c[0], (unsigned long long)c[1], (unsigned long long)c[2],
-                   (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[5],
-                   (unsigned long long)c[7]);
-    const bool cf = a->pats[0].cf;
-    const int nt = (int)std::min<int64_t>(4096, cf ? a->pats[0].cf_chunk / kCfTile
-                                                   : a->pats[0].chunk / (kPartThreads * kPartItems));
-    std::vector<uint64_t> pt((size_t)nt * 16);
-    hipMemcpy(pt.data(), (uint64_t*)a->stamps.p + 4096 * 16, pt.size() * 8, hipMemcpyDeviceToHost);
-    double ps[16] = {0};
-    uint64_t plo = UINT64_MAX, phi = 0;
-    for (int b = 0; b < nt; ++b) {
-      for (int i = 1; i < 8; ++i)
-        if (pt[b * 16 + i] && pt[b * 16 + i - 1]) ps[i] += (double)(pt[b * 16 + i] - pt[b * 16 + i - 1]);
-      if (pt[b * 16]) plo = std::min(plo, pt[b * 16]);
-      for (int i = 0; i < 8; ++i) phi = std::max(phi, pt[b * 16 + i]);
-    }
-    std::fprintf(stderr, "[cep stamps] partition phase ticks/block:");
-    for (int i = 1; i < 8; ++i) std::fprintf(stderr, " p%d=%.0f", i, ps[i] / nt);
-    std::fprintf(stderr, " span=%.0f\n", (double)(phi - plo));
-  }
-  if (a->stamps.p && !a->mqs.empty()) {
-    // diagnostics: mean ticks per multi-query walk phase over the last launch's buckets
-    const int nb = 1 << a->mqs[0].lg;
-    std::vector<uint64_t> st((size_t)nb * 16);
-    hipMemcpy(st.data(), a->stamps.p, st.size() * 8, hipMemcpyDeviceToHost);
-    double sum[8] = {0}, ut[8] = {0}, p1 = 0, rs = 0;
-    for (int b = 0; b < nb; ++b) {
-      const uint64_t* x = &st[(size_t)b * 16];
-      for (int i = 1; i < 5; ++i)
-        if (x[i] && x[i - 1]) sum[i] += (double)(x[i] - x[i - 1]);
-      if (x[5] && x[2]) p1 += (double)(x[5] - x[2]);
-      if (x[3] && x[5]) rs += (double)(x[3] - x[5]);
-      for (int i = 0; i < 8; ++i) ut[i] += (double)x[8 + i];
-    }
-    std::fprintf(stderr, "[cep stamps] mq walk ticks/bucket: gather=%.0f sort=%.0f count=%.0f (pass1 %.0f, "
-                 "reserve %.0f) emit=%.0f\n", sum[1] / nb, sum[2] / nb, sum[3] / nb, p1 / nb, rs / nb, sum[4] / nb);
-    std::fprintf(stderr, "[cep stamps] mq unit ticks/bucket (units 0-3) pass1: %.0f %.0f %.0f %.0f pass2: %.0f %.0f "
-                 "%.0f %.0f\n", ut[0] / nb, ut[1] / nb, ut[2] / nb, ut[3] / nb, ut[4] / nb, ut[5] / nb,
-                 ut[6] / nb, ut[7] / nb);
-  }
+  // every stream idle before anything is freed (the members' destructors free;
+  // their order is documented at cep_app)
+  for (hipStream_t s : {a->stream.h, a->copy.h, a->side.h, a->rstream.h})
+    if (s) hipStreamSynchronize(s);
+  dump_stamps(a);
   harvest_timers(a);
-  for (auto e : a->event_pool) hipEventDestroy(e);
-  for (auto& o : a->outs) {
-    for (auto& c : o.cols) dev_free(&c);
-    dev_free(&o.ts);
-    dev_free(&o.seq);
-    for (auto& c : o.scols) dev_free(&c);
-    dev_free(&o.sts);
-    dev_free(&o.sseq);
-  }
-  for (DevBuf* b : {&a->ostats, &a->okeys[0], &a->okeys[1], &a->oidx[0], &a->oidx[1], &a->otemp, &a->out_counts})
-    dev_free(b);
-  for (auto& p : a->pats) {
-    dev_free(&p.khdr);
-    dev_free(&p.kslot);
-    dev_free(&p.kext);
-    dev_free(&p.pool[0]);
-    dev_free(&p.pool[1]);
-    dev_free(&p.pool_cur);
-    dev_free(&p.atol_gate);
-    dev_free(&p.hwm);
-    for (DevBuf* b : {&p.tkey, &p.tval, &p.krev, &p.kcount, &p.dense}) dev_free(b);
-    for (DevBuf* b : {&p.hot_id, &p.hot_key, &p.hot_m, &p.hot_gbase, &p.hoff, &p.cand, &p.ncand, &p.harr, &p.hrow,
-                      &p.hnb, &p.bsum, &p.bcnt, &p.boff, &p.hcm, &p.hobase, &p.hot_active, &p.htmn,
-                      &p.htmx, &p.hflag, &p.btol})
-      dev_free(b);
-    host_free(&p.hot_active_host);
-    if (p.hot_fork) hipEventDestroy(p.hot_fork);
-    if (p.hot_join) hipEventDestroy(p.hot_join);
-    for (int b = 0; b < 2; ++b) {
-      dev_free(&p.recs[b]);
-      dev_free(&p.tile_off[b]);
-      dev_free(&p.cf_recs[b]);
-      dev_free(&p.cf_toff[b]);
-      dev_free(&p.chunk_base[b]);
-    }
-  }
-  for (auto& g : a->mqs) {
-    for (DevBuf* b : {&g.dq, &g.du, &g.dconds, &g.state}) dev_free(b);
-    for (int b = 0; b < 2; ++b) {
-      dev_free(&g.recs[b]);
-      dev_free(&g.toff[b]);
-      dev_free(&g.chunk_base[b]);
-    }
-  }
-  for (auto& jr : a->joins) {
-    for (DevBuf* b : {&jr.flag, &jr.bsum, &jr.boff, &jr.probe, &jr.pcnt, &jr.pbsum, &jr.pboff, &jr.st, &jr.list[0][0],
-                      &jr.list[0][1], &jr.list[1][0], &jr.list[1][1]})
-      dev_free(b);
-    host_free(&jr.total);
-  }
-  for (auto& tr : a->tabs) {
-    for (DevBuf* b : {&tr.thdr, &tr.tword, &tr.recs[0], &tr.recs[1], &tr.tile_off[0], &tr.tile_off[1],
-                      &tr.chunk_base[0], &tr.chunk_base[1]})
-      dev_free(b);
-    for (int b = 0; b < 2; ++b) {
-      if (tr.part_done[b]) hipEventDestroy(tr.part_done[b]);
-      if (tr.walk_done[b]) hipEventDestroy(tr.walk_done[b]);
-    }
-  }
-  dev_free(&a->tab_dropped);
-  if (a->copy) hipStreamSynchronize(a->copy);
-  for (auto& h : a->hs) {
-    host_free(&h.pinned);
-    dev_free(&h.dev);
-    if (h.dma_done) hipEventDestroy(h.dma_done);
-    if (h.free) hipEventDestroy(h.free);
-  }
-  for (auto& o : a->outs) {
-    for (auto& h : o.hcols) host_free(&h);
-    host_free(&o.hts);
-    host_free(&o.hseq);
-  }
-  for (int c = 0; c < kMaxCols; ++c) {
-    dev_free(&a->ro.col[c]);
-    dev_free(&a->ro.out[c]);
-  }
-  for (DevBuf* b : {&a->ro.ts, &a->ro.stream, &a->ro.ots, &a->ro.ostream, &a->ro.keys, &a->ro.idx_in,
-                    &a->ro.idx_out, &a->ro.temp, &a->ro.bound})
-    dev_free(b);
-  dev_free(&a->code);
-  dev_free(&a->konst);
-  dev_free(&a->last_ts_dev);
-  dev_free(&a->tile_state);
-  dev_free(&a->route_arena);
-  dev_free(&a->route_tcount);
-  dev_free(&a->route_toffs);
-  dev_free(&a->route_dcount);
-  dev_free(&a->ticket);
-  dev_free(&a->err);
-  dev_free(&a->rerr);
-  dev_free(&a->str_hash);
-  host_free(&a->flush_words);
-  for (auto& d : a->rr_col) dev_free(&d);
-  for (auto& v : a->views)
-    for (auto& st : v) {
-      dev_free(&st.stream);
-      for (auto& d : st.col) dev_free(&d);
-    }
-  dev_free(&a->rr_ts);
-  dev_free(&a->rr_stream);
-  dev_free(&a->rr_seq);
-  if (a->stream) hipStreamSynchronize(a->stream);
-  if (a->side) hipStreamSynchronize(a->side);
-  for (auto& p : a->pats)
-    for (int b = 0; b < 2; ++b) {
-      if (p.part_done[b]) hipEventDestroy(p.part_done[b]);
-      if (p.walk_done[b]) hipEventDestroy(p.walk_done[b]);
-    }
-  for (auto& g : a->mqs)
-    for (int b = 0; b < 2; ++b) {
-      if (g.part_done[b]) hipEventDestroy(g.part_done[b]);
-      if (g.walk_done[b]) hipEventDestroy(g.walk_done[b]);
-    }
-  if (a->in_ready) hipEventDestroy(a->in_ready);
-  if (a->ext_ready) hipEventDestroy(a->ext_ready);
-  if (a->out_ready) hipEventDestroy(a->out_ready);
-  if (a->r_ready) hipEventDestroy(a->r_ready);
-  if (a->r_host) hipEventDestroy(a->r_host);
-  if (a->rstream) {
-    hipStreamSynchronize(a->rstream);
-    hipStreamDestroy(a->rstream);
-  }
-  if (a->side) hipStreamDestroy(a->side);
-  if (a->copy) hipStreamDestroy(a->copy);
-  if (a->stream) hipStreamDestroy(a->stream);
   delete a;
 }
 
@@ -3085,7 +1917,9 @@ int cep_set_callback(cep_app* a, const char* out_id, cep_emit_fn fn, void* user)
   return CEP_OK;
 }
 
-namespace {
+}  // extern "C"
+
+namespace cep {
 
 // Batch -> device rows (host batches are staged into device memory: the
 // PCIe-inclusive path).  Validates the handle and the column count.
@@ -3126,8 +1960,7 @@ int batch_rows(cep_app* a, const cep_batch* b, RowsArgs* out, int* slot, bool* d
     auto& h = a->hs[a->hs_next];
     *slot = a->hs_next;
     a->hs_next ^= 1;
-    if (!h.dma_done && (hipEventCreateWithFlags(&h.dma_done, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&h.free, hipEventDisableTiming) != hipSuccess))
+    if (!h.dma_done && (!h.dma_done.create() || !h.free.create()))
       return fail(a, CEP_E_DEVICE, "hipEventCreate failed");
     const int nc = b->ncols;
     size_t off[kMaxCols + 2], len[kMaxCols + 2];
@@ -3177,7 +2010,9 @@ int batch_rows(cep_app* a, const cep_batch* b, RowsArgs* out, int* slot, bool* d
   return CEP_OK;
 }
 
-}  // namespace
+}  // namespace cep
+
+extern "C" {
 
 int cep_send_batch(cep_app* a, const cep_batch* b) {
   if (!a || !b) return CEP_E_ARG;
@@ -3581,249 +2416,105 @@ const char* cep_last_error(cep_app* a) { return a ? a->last_error.c_str() : "nul
 
 void cep_free(void* p) { std::free(p); }
 
-// Snapshot format (little endian), version 4:
-//   "CEPS" u32 version, u64 plan_hash, i64 events_in, u32 n_patterns,
-//   per pattern: i64 key_capacity, u32 S, u32 slot_words, u32 n_live,
-//                n_live x { u32 key, u64 header, u32 n, n * slot_words u64 }
-//                (n = pending partials, inline slots then the overflow run;
-//                versions 2 / 3 have no n: n = header & 0xff)
-//   (version >= 3) the event-time reorder buffer ("queuedRecordsState",
-//   AbstractSiddhiOperator.java:98): i32 input (-1: empty), u8 has_stream,
-//   i64 n, i64 released_max, then n rows: every column of the input's
-//   definition (type width each), n x i64 ts, n x u8 stream if has_stream;
-//   (version 4) per pattern: u8 sparse keys, if set u32 count, u32 id of
-//   the value -1 (0xffffffff: none), count x i64 partition value per dense slot.
-//   (version 5) u32 n_groups, per multi-query group: i64 key_capacity,
-//   u32 words per key, u32 n_live, n_live x { u32 key, words x u64 }.
-//   (version 6, written only by apps that hold a join; others still write 5)
-//   u32 n_joins, per join: u32 entry words, per side: u64 rows kept so far,
-//   u64 tail entries, tail x entry words u64 (the side's live rows, oldest first).
-// Versions 2 (no reorder section), 3 and 4 are still restored (apps without
-// multi-query groups).
-static uint64_t plan_hash(const CompiledApp& app) {
-  uint64_t h = 1469598103934665603ull;
-  auto mix = [&](const void* p, size_t n) {
-    const uint8_t* b = (const uint8_t*)p;
-    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
-  };
-  mix(app.code.data(), app.code.size() * sizeof(Ins));
-  mix(app.konst.data(), app.konst.size() * 8);
-  // window kind and parameter (plans without a window hash as before)
-  for (size_t qi = 0; qi < app.queries.size(); ++qi) {
-    const Query& q = app.queries[qi];
-    if (q.win_kind == WIN_NONE) continue;
-    const int64_t w[4] = {(int64_t)qi, q.win_kind, q.win_param, q.win_global ? 1 : 0};
-    mix(w, sizeof(w));
+}  // extern "C"
+
+// Snapshots: the byte format and its validation live in snapshot.h /
+// snapshot.cpp; here device state is pulled into, or committed from, a SnapImage.
+static SnapGeometry snap_geometry(cep_app* a) {
+  SnapGeometry g;
+  g.plan_hash = plan_hash(a->app);
+  g.hdr_ovf = kHdrOvf;
+  g.join_tail_cap = kJoinTailCap;
+  for (auto& rt : a->pats)
+    g.pats.push_back({rt.pa.key_capacity, rt.kstride, rt.pool_cap, rt.pa.buckets_log2, (uint32_t)rt.pa.pending_slots,
+                      (uint32_t)rt.pa.slot_words, rt.kext.p != nullptr, rt.sparse, rt.table_cap});
+  for (auto& m : a->mqs) g.groups.push_back({m.key_capacity, m.kstride, m.lg, m.kpb, (uint32_t)m.words});
+  for (auto& jr : a->joins)
+    g.joins.push_back({(uint32_t)jr.ja.ew, {jr.ja.win_kind[0], jr.ja.win_kind[1]}, {jr.ja.win_param[0], jr.ja.win_param[1]}});
+  for (auto& tr : a->tabs)
+    g.tabs.push_back({tr.pa.key_capacity, tr.kstride, tr.pa.buckets_log2, (uint32_t)tr.ta.nwords});
+  for (auto& in : a->app.inputs) {
+    g.inputs.emplace_back();
+    for (auto& at : in.attrs) g.inputs.back().push_back(type_width(at.type));
   }
-  // joins: sides, windows, carried columns (plans without a join hash as before)
-  for (size_t qi = 0; qi < app.queries.size(); ++qi) {
-    const Query& q = app.queries[qi];
-    if (q.kind != Q_JOIN) continue;
-    const int64_t w[8] = {-3, (int64_t)qi, q.a_stream, q.b_stream, q.join_side[0].win_kind, q.join_side[0].win_param,
-                          q.join_side[1].win_kind, q.join_side[1].win_param};
-    mix(w, sizeof(w));
-    for (int c : q.rec_cols_a) mix(&c, sizeof(c));
-  }
-  // tables: definitions and operations (plans without a table hash as before)
-  for (size_t ti = 0; ti < app.tables.size(); ++ti) {
-    const TableDef& T = app.tables[ti];
-    const int64_t w[4] = {-4, (int64_t)ti, T.pk, (int64_t)T.schema.attrs.size()};
-    mix(w, sizeof(w));
-    mix(T.schema.id.data(), T.schema.id.size());
-    for (auto& at : T.schema.attrs) {
-      mix(at.name.data(), at.name.size());
-      mix(&at.type, sizeof(at.type));
-    }
-    for (int qi : T.ops) {
-      const Query& q = app.queries[qi];
-      const int64_t o[6] = {-5, qi, q.tab_op, q.in_stream, q.tab_key_col, q.tab_negate ? 1 : 0};
-      mix(o, sizeof(o));
-      mix(q.tab_ins, sizeof(q.tab_ins));
-      mix(q.tab_set, sizeof(q.tab_set));
-    }
-  }
-  // query chaining (plans without derived streams hash as before)
-  for (auto& d : app.derived) {
-    const int64_t w[5] = {-1, d.stream, d.producer, d.source, d.stage};
-    mix(w, sizeof(w));
-  }
-  for (size_t qi = 0; qi < app.queries.size(); ++qi) {
-    if (app.queries[qi].view < 0) continue;
-    const int64_t w[3] = {-2, (int64_t)qi, app.queries[qi].view};
-    mix(w, sizeof(w));
-    for (int di : app.views[app.queries[qi].view].derived) mix(&di, sizeof(di));
-  }
-  return h;
+  return g;
 }
+
+template <class T>
+static void pull(std::vector<T>& v, size_t n, const void* dev) {
+  v.resize(n);
+  if (n) hipMemcpy(v.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost);
+}
+
+template <class T>
+static void push(void* dev, const std::vector<T>& v) {
+  if (!v.empty()) hipMemcpy(dev, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+extern "C" {
 
 int cep_snapshot(cep_app* a, uint8_t** buf, size_t* len) {
   if (!a || !buf || !len) return CEP_E_ARG;
   if (hipStreamSynchronize(a->stream) != hipSuccess) return fail(a, CEP_E_DEVICE, "device failure");
-  std::vector<uint8_t> out;
-  auto put = [&](const void* p, size_t n) {
-    const uint8_t* b = (const uint8_t*)p;
-    out.insert(out.end(), b, b + n);
-  };
-  const char magic[4] = {'C', 'E', 'P', 'S'};
-  put(magic, 4);
-  // 3: + the event-time reorder buffer; 4: + pending counts (overflow runs); 5: + groups; 6: + joins
-  uint32_t ver = !a->tabs.empty() ? 7 : a->joins.empty() ? 5 : 6;
-  put(&ver, 4);
-  uint64_t h = plan_hash(a->app);
-  put(&h, 8);
-  put(&a->events_in, 8);
-  uint32_t np = (uint32_t)a->pats.size();
-  put(&np, 4);
-  for (auto& rt : a->pats) {
-    const int64_t kc = rt.pa.key_capacity, ks = rt.kstride;
-    const uint32_t S = rt.pa.pending_slots, sw = rt.pa.slot_words;
-    const int lg = rt.pa.buckets_log2;
-    const int64_t kpb = ks >> lg;
-    std::vector<uint32_t> hdr(ks);
-    std::vector<uint64_t> slots((size_t)ks * S * sw), ext, pool;
-    hipMemcpy(hdr.data(), rt.khdr.p, hdr.size() * 4, hipMemcpyDeviceToHost);
-    hipMemcpy(slots.data(), rt.kslot.p, slots.size() * 8, hipMemcpyDeviceToHost);
+  SnapImage img;
+  img.geo = snap_geometry(a);
+  img.events_in = a->events_in;
+  img.pats.resize(a->pats.size());
+  for (size_t pi = 0; pi < a->pats.size(); ++pi) {
+    const PatternRT& rt = a->pats[pi];
+    auto& p = img.pats[pi];
+    const size_t ks = (size_t)rt.kstride, sw = (size_t)rt.pa.slot_words;
+    pull(p.hdr, ks, rt.khdr.p);
+    pull(p.slots, ks * rt.pa.pending_slots * sw, rt.kslot.p);
     if (rt.kext.p) {
-      ext.resize(ks);
-      pool.resize((size_t)rt.pool_cap * sw);
-      hipMemcpy(ext.data(), rt.kext.p, ext.size() * 8, hipMemcpyDeviceToHost);
-      hipMemcpy(pool.data(), rt.pool[rt.pool_side].p, pool.size() * 8, hipMemcpyDeviceToHost);
+      pull(p.ext, ks, rt.kext.p);
+      pull(p.pool, (size_t)rt.pool_cap * sw, rt.pool[rt.pool_side].p);
     }
-    uint32_t live = 0;
-    for (int64_t i = 0; i < ks; ++i) live += hdr[i] ? 1 : 0;
-    put(&kc, 8);
-    put(&S, 4);
-    put(&sw, 4);
-    put(&live, 4);
-    for (int64_t i = 0; i < ks; ++i) {
-      if (!hdr[i]) continue;
-      const uint32_t key = (uint32_t)(((i % kpb) << lg) | (i / kpb));   // dense key
-      const bool ovf = (hdr[i] & kHdrOvf) && !ext.empty();
-      const uint64_t h64 = hdr[i] & ~(uint64_t)kHdrOvf;
-      const uint32_t n = ovf ? (uint32_t)ext[i] : (hdr[i] & 0xff);
-      const uint64_t off = ovf ? ext[i] >> 32 : 0;
-      put(&key, 4);
-      put(&h64, 8);
-      put(&n, 4);
-      for (uint32_t j = 0; j < n; ++j)
-        for (uint32_t w = 0; w < sw; ++w)
-          put(j < S ? &slots[((size_t)j * sw + w) * ks + i] : &pool[(off + j - S) * sw + w], 8);
+    if (rt.sparse) {
+      hipMemcpy(p.kcount, rt.kcount.p, 8, hipMemcpyDeviceToHost);
+      p.kcount[0] = std::min<uint32_t>(p.kcount[0], (uint32_t)rt.pa.key_capacity);
+      pull(p.krev, p.kcount[0], rt.krev.p);
     }
   }
-  // rows waiting for a watermark (the operator checkpoints its PriorityQueue
-  // as "queuedRecordsState": AbstractSiddhiOperator.java:98, 396-404)
   {
     const auto& r = a->ro;
-    const int32_t in = r.n > 0 ? r.input : -1;
-    const uint8_t hs = r.has_stream ? 1 : 0;
-    put(&in, 4);
-    put(&hs, 1);
-    put(&r.n, 8);
-    put(&r.released_max, 8);
+    img.ro.input = r.input;
+    img.ro.has_stream = r.has_stream;
+    img.ro.n = r.n;
+    img.ro.released_max = r.released_max;
     if (r.n > 0) {
       const StreamSchema& sd = a->app.inputs[r.input];
       std::vector<uint8_t> tmp;
-      auto pull = [&](const DevBuf& b, size_t bytes) {
-        tmp.resize(bytes);
-        hipMemcpy(tmp.data(), b.p, bytes, hipMemcpyDeviceToHost);
-        put(tmp.data(), bytes);
+      auto col = [&](const DevBuf& b, size_t bytes) {
+        pull(tmp, bytes, b.p);
+        img.ro.rows.insert(img.ro.rows.end(), tmp.begin(), tmp.end());
       };
-      for (size_t c = 0; c < sd.attrs.size(); ++c) pull(r.col[c], (size_t)r.n * type_width(sd.attrs[c].type));
-      pull(r.ts, (size_t)r.n * 8);
-      if (r.has_stream) pull(r.stream, (size_t)r.n);
+      for (size_t c = 0; c < sd.attrs.size(); ++c) col(r.col[c], (size_t)r.n * type_width(sd.attrs[c].type));
+      col(r.ts, (size_t)r.n * 8);
+      if (r.has_stream) col(r.stream, (size_t)r.n);
     }
   }
-  // (version 4) per pattern: the sparse-key map, dense slot -> value
-  for (auto& rt : a->pats) {
-    const uint8_t sp = rt.sparse ? 1 : 0;
-    put(&sp, 1);
-    if (!sp) continue;
-    uint32_t cnt[2];
-    hipMemcpy(cnt, rt.kcount.p, 8, hipMemcpyDeviceToHost);
-    cnt[0] = std::min<uint32_t>(cnt[0], (uint32_t)rt.pa.key_capacity);
-    put(cnt, 8);
-    std::vector<uint64_t> rev(cnt[0]);
-    if (cnt[0]) hipMemcpy(rev.data(), rt.krev.p, rev.size() * 8, hipMemcpyDeviceToHost);
-    put(rev.data(), rev.size() * 8);
-  }
-  // (version 5) multi-query groups: per group every key whose state is not
-  // all zero, with the group's state words (query by query, plan order)
-  {
-    const uint32_t ng = (uint32_t)a->mqs.size();
-    put(&ng, 4);
-    for (auto& g : a->mqs) {
-      const int64_t ks = g.kstride, kpb = g.kpb;
-      const uint32_t nw = (uint32_t)g.words;
-      std::vector<uint64_t> st((size_t)g.words * ks);
-      hipMemcpy(st.data(), g.state.p, st.size() * 8, hipMemcpyDeviceToHost);
-      std::vector<uint32_t> live;
-      // state word w of bucket-major key index i = b * kpb + k lives at
-      // (b * words + w) * kpb + k (each bucket's state is one contiguous block)
-      auto sidx = [&](int64_t i, uint32_t w) { return (size_t)(((i / kpb) * nw + w) * kpb + i % kpb); };
-      for (int64_t i = 0; i < ks; ++i) {
-        bool any = false;
-        for (uint32_t w = 0; w < nw && !any; ++w) any = st[sidx(i, w)] != 0;
-        if (any) live.push_back((uint32_t)i);
-      }
-      const uint32_t nl = (uint32_t)live.size();
-      put(&g.key_capacity, 8);
-      put(&nw, 4);
-      put(&nl, 4);
-      for (uint32_t i : live) {
-        const uint32_t key = (uint32_t)(((i % kpb) << g.lg) | (i / kpb));   // dense key
-        put(&key, 4);
-        for (uint32_t w = 0; w < nw; ++w) put(&st[sidx(i, w)], 8);
-      }
+  img.groups.resize(a->mqs.size());
+  for (size_t gi = 0; gi < a->mqs.size(); ++gi)
+    pull(img.groups[gi], (size_t)a->mqs[gi].words * a->mqs[gi].kstride, a->mqs[gi].state.p);
+  img.joins.resize(a->joins.size());
+  for (size_t ji = 0; ji < a->joins.size(); ++ji) {
+    const JoinRT& jr = a->joins[ji];
+    JoinState st;
+    hipMemcpy(&st, jr.st.p, sizeof(st), hipMemcpyDeviceToHost);
+    for (int sd = 0; sd < 2; ++sd) {
+      img.joins[ji].kept[sd] = st.kept[sd];
+      img.joins[ji].tail[sd] = std::min<uint64_t>(st.tail[sd], (uint64_t)jr.list_cap[sd]);
+      pull(img.joins[ji].rows[sd], (size_t)img.joins[ji].tail[sd] * jr.ja.ew, jr.list[sd][jr.cur].p);
     }
   }
-  // (version 6) joins: each side's live rows (the list's tail) and counts
-  if (ver >= 6) {
-    const uint32_t nj = (uint32_t)a->joins.size();
-    put(&nj, 4);
-    for (auto& jr : a->joins) {
-      JoinState st;
-      hipMemcpy(&st, jr.st.p, sizeof(st), hipMemcpyDeviceToHost);
-      const uint32_t ew = (uint32_t)jr.ja.ew;
-      put(&ew, 4);
-      for (int sd = 0; sd < 2; ++sd) {
-        const uint64_t tail = std::min<uint64_t>(st.tail[sd], (uint64_t)jr.list_cap[sd]);
-        put(&st.kept[sd], 8);
-        put(&tail, 8);
-        std::vector<uint64_t> rows((size_t)tail * ew);
-        if (tail) hipMemcpy(rows.data(), jr.list[sd][jr.cur].p, rows.size() * 8, hipMemcpyDeviceToHost);
-        put(rows.data(), rows.size() * 8);
-      }
-    }
+  img.tabs.resize(a->tabs.size());
+  for (size_t ti = 0; ti < a->tabs.size(); ++ti) {
+    pull(img.tabs[ti].hdr, (size_t)a->tabs[ti].kstride, a->tabs[ti].thdr.p);
+    pull(img.tabs[ti].words, (size_t)a->tabs[ti].kstride * a->tabs[ti].ta.nwords, a->tabs[ti].tword.p);
   }
-  // (version 7) tables: per table its live rows, by dense key
-  if (ver >= 7) {
-    const uint32_t nt = (uint32_t)a->tabs.size();
-    put(&nt, 4);
-    for (auto& tr : a->tabs) {
-      const int64_t ks = tr.kstride, kc = tr.pa.key_capacity;
-      const int lg = tr.pa.buckets_log2;
-      const int64_t kpb = ks >> lg;
-      const uint32_t nw = (uint32_t)tr.ta.nwords;
-      std::vector<uint32_t> hdr(ks);
-      std::vector<uint64_t> words((size_t)ks * nw);
-      hipMemcpy(hdr.data(), tr.thdr.p, hdr.size() * 4, hipMemcpyDeviceToHost);
-      hipMemcpy(words.data(), tr.tword.p, words.size() * 8, hipMemcpyDeviceToHost);
-      uint32_t live = 0;
-      for (int64_t i = 0; i < ks; ++i) live += hdr[i] & 1u;
-      put(&kc, 8);
-      put(&nw, 4);
-      put(&live, 4);
-      for (int64_t i = 0; i < ks; ++i) {
-        if (!(hdr[i] & 1u)) continue;
-        const uint32_t key = (uint32_t)(((i % kpb) << lg) | (i / kpb));   // dense key
-        put(&key, 4);
-        for (uint32_t w = 0; w < nw; ++w) put(&words[(size_t)w * ks + i], 8);
-      }
-    }
-    unsigned long long d = 0;
-    hipMemcpy(&d, a->tab_dropped.p, 8, hipMemcpyDeviceToHost);
-    put(&d, 8);
-  }
+  if (a->tab_dropped.p) hipMemcpy(&img.tab_dropped, a->tab_dropped.p, 8, hipMemcpyDeviceToHost);
+  const std::vector<uint8_t> out = snapshot_encode(img);
   *buf = (uint8_t*)std::malloc(out.size());
   if (!*buf) return fail(a, CEP_E_DEVICE, "out of host memory");
   std::memcpy(*buf, out.data(), out.size());
@@ -3833,308 +2524,82 @@ int cep_snapshot(cep_app* a, uint8_t** buf, size_t* len) {
 
 int cep_restore(cep_app* a, const uint8_t* buf, size_t len) {
   if (!a || (!buf && len)) return CEP_E_ARG;
-  size_t off = 0;
-  auto get = [&](void* p, size_t n) -> bool {
-    if (n > len - off) return false;
-    std::memcpy(p, buf + off, n);
-    off += n;
-    return true;
-  };
-  char magic[4];
-  uint32_t ver;
-  uint64_t h;
-  int64_t ev;
-  uint32_t np;
-  if (!get(magic, 4) || std::memcmp(magic, "CEPS", 4) || !get(&ver, 4) || ver < 2 || ver > 7 || !get(&h, 8) ||
-      !get(&ev, 8) || !get(&np, 4))
-    return fail(a, CEP_E_STATE, "not a libcep snapshot");
-  if (h != plan_hash(a->app) || np != a->pats.size())
-    return fail(a, CEP_E_STATE, "snapshot was taken with a different plan (or a build that compiled it "
-                                "differently: 2-state patterns with s1-dependent conditions need CEP_PAIR_WALK=1 "
-                                "to restore snapshots of builds before round 4)");
-  // Phase 1: parse and validate everything into host buffers; nothing on the
-  // device changes until the whole snapshot is known to be good.
-  struct PatState {
-    std::vector<uint32_t> hdr;
-    std::vector<uint64_t> slots, ext, pool;
-    uint64_t pool_used = 0;
-    int64_t ts_max = INT64_MIN;   // largest partial ts (the closed form's high-water mark)
-  };
-  std::vector<PatState> ps(a->pats.size());
-  for (size_t pi = 0; pi < a->pats.size(); ++pi) {
-    const PatternRT& rt = a->pats[pi];
-    int64_t kc;
-    uint32_t S, sw, live;
-    if (!get(&kc, 8) || !get(&S, 4) || !get(&sw, 4) || !get(&live, 4))
-      return fail(a, CEP_E_STATE, "truncated snapshot");
-    if (kc != rt.pa.key_capacity || S != (uint32_t)rt.pa.pending_slots ||
-        sw != (uint32_t)rt.pa.slot_words)
-      return fail(a, CEP_E_STATE, "snapshot geometry differs from this runtime");
-    if ((uint64_t)live > (uint64_t)kc) return fail(a, CEP_E_STATE, "corrupt snapshot (live keys)");
-    const int64_t ks = rt.kstride;
-    const int lg = rt.pa.buckets_log2;
-    const int64_t kpb = ks >> lg;
-    ps[pi].hdr.assign(ks, 0);
-    ps[pi].slots.assign((size_t)ks * S * sw, 0);
-    if (rt.kext.p) ps[pi].ext.assign(ks, 0);
-    for (uint32_t i = 0; i < live; ++i) {
-      uint32_t key, nk;
-      uint64_t h64;
-      if (!get(&key, 4) || !get(&h64, 8) || key >= kc || (h64 & kHdrOvf))
-        return fail(a, CEP_E_STATE, "corrupt snapshot");
-      if (ver >= 4) {
-        if (!get(&nk, 4)) return fail(a, CEP_E_STATE, "truncated snapshot");
-      } else {
-        nk = (uint32_t)(h64 & 0xff);
-      }
-      if ((uint64_t)nk * sw > (len - off) / 8) return fail(a, CEP_E_STATE, "truncated snapshot");
-      const int64_t idx = (int64_t)(key & ((1u << lg) - 1)) * kpb + (key >> lg);
-      uint32_t hw = (uint32_t)h64;
-      if (nk > S) {   // overflow run: the pending pool (closed-form runtimes only)
-        if (ps[pi].ext.empty())
-          return fail(a, CEP_E_CAPACITY, "snapshot holds more than pending_slots partials for a key");
-        if (ps[pi].pool_used + (nk - S) > (uint64_t)rt.pool_cap)
-          return fail(a, CEP_E_CAPACITY, "snapshot's overflow partials exceed the pending pool");
-        ps[pi].ext[idx] = (uint64_t)nk | (ps[pi].pool_used << 32);
-        ps[pi].pool.resize((ps[pi].pool_used + (nk - S)) * sw);
-        hw = (hw & ~0xffu) | (uint32_t)S | kHdrOvf;
-      } else {
-        hw = (hw & ~0xffu) | nk;
-      }
-      for (uint32_t j = 0; j < nk; ++j)
-        for (uint32_t w = 0; w < sw; ++w) {
-          uint64_t* dst = j < S ? &ps[pi].slots[((size_t)j * sw + w) * ks + idx]
-                                : &ps[pi].pool[(ps[pi].pool_used + j - S) * sw + w];
-          if (!get(dst, 8)) return fail(a, CEP_E_STATE, "truncated snapshot");
-          if (w == 0) ps[pi].ts_max = std::max(ps[pi].ts_max, (int64_t)*dst);
-        }
-      if (nk > S) ps[pi].pool_used += nk - S;
-      ps[pi].hdr[idx] = hw;
-    }
-  }
-  int32_t in = -1;
-  uint8_t hs = 0;
-  int64_t n = 0, rmax = INT64_MIN;
-  size_t rows_off = 0;
-  if (ver >= 3) {
-    if (!get(&in, 4) || !get(&hs, 1) || !get(&n, 8) || !get(&rmax, 8) || n < 0 || n > (int64_t)INT32_MAX ||
-        (n > 0 && (in < 0 || in >= (int)a->app.inputs.size())))
-      return fail(a, CEP_E_STATE, "corrupt snapshot (reorder buffer)");
-    if (n > 0) {
-      size_t row_bytes = 8 + (hs ? 1 : 0);
-      for (auto& at : a->app.inputs[in].attrs) row_bytes += (size_t)type_width(at.type);
-      if ((uint64_t)n > (len - off) / row_bytes)
-        return fail(a, CEP_E_STATE, "truncated snapshot (reorder buffer)");
-      rows_off = off;
-      off += (size_t)n * row_bytes;
-    }
-  }
-  // sparse-key maps: rebuilt here as device tables (same hash and probing
-  // as keymap.hip; any valid placement serves lookups)
-  struct KeyMap {
-    std::vector<uint64_t> tkey, rev;
-    std::vector<uint32_t> tval;
-    uint32_t cnt[2] = {0, 0xffffffffu};
-  };
-  std::vector<KeyMap> km(a->pats.size());
-  if (ver >= 4) {
-    for (size_t pi = 0; pi < a->pats.size(); ++pi) {
-      const PatternRT& rt = a->pats[pi];
-      uint8_t sp;
-      if (!get(&sp, 1) || (sp != 0) != rt.sparse) return fail(a, CEP_E_STATE, "snapshot key map does not match");
-      if (!sp) continue;
-      KeyMap& m = km[pi];
-      if (!get(m.cnt, 8) || m.cnt[0] > (uint64_t)rt.pa.key_capacity || (uint64_t)m.cnt[0] > (len - off) / 8)
-        return fail(a, CEP_E_STATE, "corrupt snapshot (key map)");
-      m.rev.resize(m.cnt[0]);
-      get(m.rev.data(), m.rev.size() * 8);
-      m.tkey.assign(rt.table_cap, 0);
-      m.tval.assign(rt.table_cap, 0xffffffffu);
-      for (uint32_t id = 0; id < m.cnt[0]; ++id) {
-        if (id == m.cnt[1]) continue;   // the value -1 has its own word
-        const uint64_t v = m.rev[id];
-        uint64_t z = v + 0x9E3779B97F4A7C15ull;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        uint64_t h = (z ^ (z >> 31)) & (rt.table_cap - 1);
-        while (m.tkey[h]) h = (h + 1) & (rt.table_cap - 1);
-        m.tkey[h] = v + 1;
-        m.tval[h] = id;
-      }
-    }
-  } else {
-    for (auto& rt : a->pats)
-      if (rt.sparse) return fail(a, CEP_E_STATE, "snapshot has no key map (version < 4)");
-  }
-  // (version 5) multi-query group state
-  std::vector<std::vector<uint64_t>> mst(a->mqs.size());
-  if (ver >= 5) {
-    uint32_t ng;
-    if (!get(&ng, 4) || ng != a->mqs.size()) return fail(a, CEP_E_STATE, "snapshot multi-query groups do not match");
-    for (size_t gi = 0; gi < a->mqs.size(); ++gi) {
-      const MqRT& g = a->mqs[gi];
-      int64_t kc;
-      uint32_t nw, nl;
-      if (!get(&kc, 8) || !get(&nw, 4) || !get(&nl, 4)) return fail(a, CEP_E_STATE, "truncated snapshot");
-      if (kc != g.key_capacity || nw != (uint32_t)g.words || nl > (uint64_t)kc)
-        return fail(a, CEP_E_STATE, "snapshot geometry differs from this runtime");
-      if ((uint64_t)nl * (4 + 8ull * nw) > len - off) return fail(a, CEP_E_STATE, "truncated snapshot");
-      mst[gi].assign((size_t)g.words * g.kstride, 0);
-      for (uint32_t i = 0; i < nl; ++i) {
-        uint32_t key;
-        get(&key, 4);
-        if (key >= kc) return fail(a, CEP_E_STATE, "corrupt snapshot");
-        const int64_t idx = (int64_t)(key & ((1u << g.lg) - 1)) * g.kpb + (key >> g.lg);
-        for (uint32_t w = 0; w < nw; ++w)
-          get(&mst[gi][(size_t)(((idx / g.kpb) * nw + w) * g.kpb + idx % g.kpb)], 8);
-      }
-    }
-  } else if (!a->mqs.empty()) {
-    // v2-v4 kept these queries on per-query runtimes: a runtime created with
-    // CEP_NO_MQ=1 has that layout and restores the snapshot
-    return fail(a, CEP_E_STATE, "snapshot has no multi-query group state (version < 5): "
-                                "create the runtime with CEP_NO_MQ=1 to restore it on per-query state");
-  }
-  // (version 6) joins
-  struct JoinSnap {
-    uint64_t kept[2] = {0, 0}, tail[2] = {0, 0};
-    std::vector<uint64_t> rows[2];
-  };
-  std::vector<JoinSnap> js(a->joins.size());
-  if (ver >= 6) {
-    uint32_t nj;
-    if (!get(&nj, 4) || nj != a->joins.size()) return fail(a, CEP_E_STATE, "snapshot joins do not match");
-    for (size_t ji = 0; ji < a->joins.size(); ++ji) {
-      const JoinRT& jr = a->joins[ji];
-      uint32_t ew;
-      if (!get(&ew, 4) || ew != (uint32_t)jr.ja.ew)
-        return fail(a, CEP_E_STATE, "snapshot geometry differs from this runtime (join rows)");
-      for (int sd = 0; sd < 2; ++sd) {
-        if (!get(&js[ji].kept[sd], 8) || !get(&js[ji].tail[sd], 8)) return fail(a, CEP_E_STATE, "truncated snapshot");
-        const uint64_t tail = js[ji].tail[sd];
-        const uint64_t max_tail = jr.ja.win_kind[sd] == WIN_LENGTH ? (uint64_t)jr.ja.win_param[sd] : (uint64_t)kJoinTailCap;
-        if (tail > max_tail || tail * ew > (len - off) / 8) return fail(a, CEP_E_STATE, "corrupt snapshot (join rows)");
-        js[ji].rows[sd].resize((size_t)tail * ew);
-        get(js[ji].rows[sd].data(), js[ji].rows[sd].size() * 8);
-      }
-    }
-  } else if (!a->joins.empty()) {
-    return fail(a, CEP_E_STATE, "snapshot has no join state (version < 6)");
-  }
-  // (version 7) tables
-  struct TabSnap {
-    std::vector<uint32_t> hdr;
-    std::vector<uint64_t> words;
-  };
-  std::vector<TabSnap> tsn(a->tabs.size());
-  unsigned long long tab_dropped = 0;
-  if (ver >= 7) {
-    uint32_t nt;
-    if (!get(&nt, 4) || nt != a->tabs.size()) return fail(a, CEP_E_STATE, "snapshot tables do not match");
-    for (size_t ti = 0; ti < a->tabs.size(); ++ti) {
-      const TableRT& tr = a->tabs[ti];
-      int64_t kc;
-      uint32_t nw, live;
-      if (!get(&kc, 8) || !get(&nw, 4) || !get(&live, 4)) return fail(a, CEP_E_STATE, "truncated snapshot");
-      if (kc != tr.pa.key_capacity || nw != (uint32_t)tr.ta.nwords || (uint64_t)live > (uint64_t)kc)
-        return fail(a, CEP_E_STATE, "snapshot geometry differs from this runtime (table rows)");
-      if ((uint64_t)live * (4 + 8ull * nw) > len - off) return fail(a, CEP_E_STATE, "truncated snapshot");
-      const int64_t ks = tr.kstride;
-      const int lg = tr.pa.buckets_log2;
-      const int64_t kpb = ks >> lg;
-      tsn[ti].hdr.assign(ks, 0);
-      tsn[ti].words.assign((size_t)ks * nw, 0);
-      for (uint32_t i = 0; i < live; ++i) {
-        uint32_t key;
-        get(&key, 4);
-        if (key >= kc) return fail(a, CEP_E_STATE, "corrupt snapshot");
-        const int64_t idx = (int64_t)(key & ((1u << lg) - 1)) * kpb + (key >> lg);
-        tsn[ti].hdr[idx] = 1;
-        for (uint32_t w = 0; w < nw; ++w) get(&tsn[ti].words[(size_t)w * ks + idx], 8);
-      }
-    }
-    if (!get(&tab_dropped, 8)) return fail(a, CEP_E_STATE, "truncated snapshot");
-  } else if (!a->tabs.empty()) {
-    return fail(a, CEP_E_STATE, "snapshot has no table state (version < 7)");
-  }
-  // Phase 2: commit (device allocations first, so a failure leaves the
-  // runtime as it was)
+  // decode and validate everything into a host image; nothing on the device
+  // changes until the whole snapshot is known to be good
+  SnapImage img;
+  std::string why;
+  if (const int rc = snapshot_decode(snap_geometry(a), buf, len, &img, &why)) return fail(a, rc, why);
+  // commit (device allocations first, so a failure leaves the runtime as it was)
   auto& r = a->ro;
+  const int64_t n = img.ro.n;
+  const StreamSchema* sd = n > 0 ? &a->app.inputs[img.ro.input] : nullptr;
   if (n > 0) {
-    const StreamSchema& sd = a->app.inputs[in];
     bool ok = true;
-    for (size_t c = 0; c < sd.attrs.size() && ok; ++c)
-      ok = dev_ensure(&r.col[c], (size_t)n * type_width(sd.attrs[c].type), a->stream, false);
+    for (size_t c = 0; c < sd->attrs.size() && ok; ++c)
+      ok = dev_ensure(&r.col[c], (size_t)n * type_width(sd->attrs[c].type), a->stream, false);
     ok = ok && dev_ensure(&r.ts, (size_t)n * 8, a->stream, false);
-    if (hs) ok = ok && dev_ensure(&r.stream, (size_t)n, a->stream, false);
+    if (img.ro.has_stream) ok = ok && dev_ensure(&r.stream, (size_t)n, a->stream, false);
     if (!ok) return fail(a, CEP_E_DEVICE, "out of device memory (reorder buffer)");
   }
   hipStreamSynchronize(a->stream);
   for (size_t pi = 0; pi < a->pats.size(); ++pi) {
     PatternRT& rt = a->pats[pi];
-    hipMemcpy(rt.khdr.p, ps[pi].hdr.data(), ps[pi].hdr.size() * 4, hipMemcpyHostToDevice);
-    hipMemcpy(rt.kslot.p, ps[pi].slots.data(), ps[pi].slots.size() * 8, hipMemcpyHostToDevice);
+    const auto& p = img.pats[pi];
+    push(rt.khdr.p, p.hdr);
+    push(rt.kslot.p, p.slots);
     if (rt.hwm.p) {   // no restored partial lies above the mark
       std::vector<uint64_t> h(128, 0ull);
-      h[0] = h[64] = (uint64_t)ps[pi].ts_max ^ (1ull << 63);
-      hipMemcpy(rt.hwm.p, h.data(), h.size() * 8, hipMemcpyHostToDevice);
+      h[0] = h[64] = (uint64_t)p.ts_max ^ (1ull << 63);
+      push(rt.hwm.p, h);
     }
     if (rt.kext.p) {
-      hipMemcpy(rt.kext.p, ps[pi].ext.data(), ps[pi].ext.size() * 8, hipMemcpyHostToDevice);
-      if (!ps[pi].pool.empty())
-        hipMemcpy(rt.pool[rt.pool_side].p, ps[pi].pool.data(), ps[pi].pool.size() * 8, hipMemcpyHostToDevice);
+      push(rt.kext.p, p.ext);
+      push(rt.pool[rt.pool_side].p, p.pool);
     }
   }
   r.n = 0;
   r.input = -1;
-  r.released_max = rmax;
+  r.released_max = img.ro.released_max;
   if (n > 0) {
-    const StreamSchema& sd = a->app.inputs[in];
-    size_t o = rows_off;
-    for (size_t c = 0; c < sd.attrs.size(); ++c) {
-      const size_t bytes = (size_t)n * type_width(sd.attrs[c].type);
-      hipMemcpy(r.col[c].p, buf + o, bytes, hipMemcpyHostToDevice);
-      o += bytes;
+    const uint8_t* src = img.ro.rows.data();
+    for (size_t c = 0; c < sd->attrs.size(); ++c) {
+      const size_t bytes = (size_t)n * type_width(sd->attrs[c].type);
+      hipMemcpy(r.col[c].p, src, bytes, hipMemcpyHostToDevice);
+      src += bytes;
     }
-    hipMemcpy(r.ts.p, buf + o, (size_t)n * 8, hipMemcpyHostToDevice);
-    o += (size_t)n * 8;
-    if (hs) hipMemcpy(r.stream.p, buf + o, (size_t)n, hipMemcpyHostToDevice);
-    r.input = in;
-    r.has_stream = hs != 0;
+    hipMemcpy(r.ts.p, src, (size_t)n * 8, hipMemcpyHostToDevice);
+    if (img.ro.has_stream) hipMemcpy(r.stream.p, src + (size_t)n * 8, (size_t)n, hipMemcpyHostToDevice);
+    r.input = img.ro.input;
+    r.has_stream = img.ro.has_stream;
     r.n = n;
   }
   for (size_t pi = 0; pi < a->pats.size(); ++pi) {
     PatternRT& rt = a->pats[pi];
     if (!rt.sparse) continue;
-    hipMemcpy(rt.tkey.p, km[pi].tkey.data(), km[pi].tkey.size() * 8, hipMemcpyHostToDevice);
-    hipMemcpy(rt.tval.p, km[pi].tval.data(), km[pi].tval.size() * 4, hipMemcpyHostToDevice);
-    if (!km[pi].rev.empty()) hipMemcpy(rt.krev.p, km[pi].rev.data(), km[pi].rev.size() * 8, hipMemcpyHostToDevice);
-    hipMemcpy(rt.kcount.p, km[pi].cnt, 8, hipMemcpyHostToDevice);
+    push(rt.tkey.p, img.pats[pi].tkey);
+    push(rt.tval.p, img.pats[pi].tval);
+    push(rt.krev.p, img.pats[pi].krev);
+    hipMemcpy(rt.kcount.p, img.pats[pi].kcount, 8, hipMemcpyHostToDevice);
   }
-  for (size_t gi = 0; gi < a->mqs.size(); ++gi)
-    hipMemcpy(a->mqs[gi].state.p, mst[gi].data(), mst[gi].size() * 8, hipMemcpyHostToDevice);
+  for (size_t gi = 0; gi < a->mqs.size(); ++gi) push(a->mqs[gi].state.p, img.groups[gi]);
   for (size_t ji = 0; ji < a->joins.size(); ++ji) {
     JoinRT& jr = a->joins[ji];
     JoinState st{};
-    for (int sd = 0; sd < 2; ++sd) {
-      st.kept[sd] = js[ji].kept[sd];
-      st.tail[sd] = st.n[sd] = js[ji].tail[sd];
-      if (!js[ji].rows[sd].empty())
-        hipMemcpy(jr.list[sd][jr.cur].p, js[ji].rows[sd].data(), js[ji].rows[sd].size() * 8, hipMemcpyHostToDevice);
+    for (int s = 0; s < 2; ++s) {
+      st.kept[s] = img.joins[ji].kept[s];
+      st.tail[s] = st.n[s] = img.joins[ji].tail[s];
+      push(jr.list[s][jr.cur].p, img.joins[ji].rows[s]);
     }
     hipMemcpy(jr.st.p, &st, sizeof(st), hipMemcpyHostToDevice);
   }
   for (size_t ti = 0; ti < a->tabs.size(); ++ti) {
-    TableRT& tr = a->tabs[ti];
-    hipMemcpy(tr.thdr.p, tsn[ti].hdr.data(), tsn[ti].hdr.size() * 4, hipMemcpyHostToDevice);
-    hipMemcpy(tr.tword.p, tsn[ti].words.data(), tsn[ti].words.size() * 8, hipMemcpyHostToDevice);
+    push(a->tabs[ti].thdr.p, img.tabs[ti].hdr);
+    push(a->tabs[ti].tword.p, img.tabs[ti].words);
   }
-  if (a->tab_dropped.p) hipMemcpy(a->tab_dropped.p, &tab_dropped, 8, hipMemcpyHostToDevice);
-  a->events_in = ev;
+  if (a->tab_dropped.p) hipMemcpy(a->tab_dropped.p, &img.tab_dropped, 8, hipMemcpyHostToDevice);
+  a->events_in = img.events_in;
   return CEP_OK;
 }
-
-static const char* kTableShuffle = "the key / row shuffle of an app that holds a table is not supported";
 
 // The live rows of table `table_id`, ordered by primary key, columns = the
 // table's attributes (ts / seq NULL).  On a shard: the keys it owns.
@@ -4190,468 +2655,6 @@ int cep_table_rows(cep_app* a, const char* table_id, cep_emit_fn fn, void* user)
   return CEP_OK;
 }
 
-int cep_record_words(cep_app* a) {
-  if (a && !a->app.tables.empty()) {
-    fail(a, CEP_E_UNSUPPORTED, kTableShuffle);
-    return -CEP_E_UNSUPPORTED;
-  }
-  if (a && !a->joins.empty()) {
-    fail(a, CEP_E_UNSUPPORTED, "key shuffle of an app that holds a join is not supported: its windows are global, "
-                               "not per key");
-    return -CEP_E_UNSUPPORTED;
-  }
-  if (!a || a->pats.size() != 1) return -CEP_E_UNSUPPORTED;
-  return a->pats[0].pa.rec_words + 1;   // wide record: [hdr, seq, ts, carried...]
-}
-
-// seg_cap == 0: owner-contiguous output, counts read back (cep_route_batch);
-// seg_cap > 0: padded owner segments with in-band counts, nothing read back
-// (cep_route_batch_padded).
-struct SpillArgs {
-  void* out = nullptr;         // nullptr: records past seg_cap are dropped (and flagged)
-  int64_t cap = 0;             // records the spill holds
-  int64_t* counts = nullptr;   // device: spilled records per owner
-};
-
-static int route_batch(cep_app* a, const cep_batch* b, int world, int64_t seq0, void* rec_out,
-                       int64_t rec_cap, int64_t* counts_host, int64_t seg_cap, const SpillArgs& sp = SpillArgs()) {
-  if (!a || !b || world <= 0 || (seg_cap == 0 && !counts_host) || seg_cap < 0) return CEP_E_ARG;
-  if (world > kMaxWorld) return fail(a, CEP_E_ARG, "world exceeds " + std::to_string(kMaxWorld));
-  if (!a->app.derived.empty())
-    return fail(a, CEP_E_UNSUPPORTED, "key shuffle of an app with query chaining (derived streams) is not supported: "
-                                      "the sender needs the key in source columns");
-  if (!a->app.tables.empty()) return fail(a, CEP_E_UNSUPPORTED, kTableShuffle);
-  if (!a->joins.empty())
-    return fail(a, CEP_E_UNSUPPORTED, "key shuffle of an app that holds a join is not supported: its windows are "
-                                      "global, not per key");
-  if (a->pats.size() != 1 || a->app.queries.size() != 1)
-    return fail(a, CEP_E_UNSUPPORTED, "key shuffle needs an app with exactly one keyed pattern");
-  PatternRT& rt = a->pats[0];
-  const Query& q = a->app.queries[rt.q];
-  if (q.key_col_a < 0 || q.key_col_b < 0)
-    return fail(a, CEP_E_UNSUPPORTED, "key shuffle needs a partitioned pattern");
-  if (seg_cap == 0) {
-    for (int d = 0; d < world; ++d) counts_host[d] = 0;
-    if (b->n == 0) return CEP_OK;
-    // the gather writes rec_out as soon as it runs: at most n records are
-    // routed, so a buffer of n records can never overrun (checked up front)
-    if (!rec_out || rec_cap < b->n)
-      return fail(a, CEP_E_ARG, "rec_out must hold at least n records (" + std::to_string(b->n) + ")");
-  } else {
-    // every rank ships world segments each step, so the null records need a
-    // ts / seq of this batch (its first and last rows)
-    if (b->n == 0) return fail(a, CEP_E_ARG, "padded key shuffle needs a non-empty batch");
-    if (!rec_out || rec_cap < (int64_t)world * (1 + seg_cap))
-      return fail(a, CEP_E_ARG, "rec_out must hold world * (1 + seg_cap) records");
-  }
-  RowsArgs rows{};
-  int slot;
-  bool direct;
-  int rc = batch_rows(a, b, &rows, &slot, &direct);
-  if (rc) return rc;
-  // fast route (k_cfroute) when every column the pattern reads is prefetchable
-  // and f / g are term lists (the k_cfpart load path); CEP_NO_CF=1 forces k_route
-  static const bool no_cf = std::getenv("CEP_NO_CF") != nullptr;
-  const bool fast = !no_cf && !rt.part_vm && rt.pref.n >= 0 && rt.pref.key_slot <= 0 &&
-                    rt.pa.rec_words + 1 <= 5 && pref_aligned(rt.pref, rows);
-  const int64_t tile_rows = fast ? kCfTile : kPartThreads * kPartItems;
-  const int64_t ntiles = (b->n + tile_rows - 1) / tile_rows;
-  const int wrw = rt.pa.rec_words + 1;
-  // device batches route on the route stream (ordered after the producer by
-  // cep_stream_wait), so the walk of the previous batch keeps running; host
-  // batches were staged on the engine stream and route there
-  hipStream_t rs = b->on_device ? a->rstream : a->stream;
-  if (!dev_ensure(&a->route_arena, (size_t)ntiles * tile_rows * wrw * 8, rs, false) ||
-      !dev_ensure(&a->route_tcount, (size_t)ntiles * world * 4, rs, false) ||
-      !dev_ensure(&a->route_toffs, (size_t)ntiles * world * 4, rs, false) ||
-      !dev_ensure(&a->route_dcount, (size_t)world * 8, rs, false))
-    return fail(a, CEP_E_DEVICE, "out of device memory (route arena)");
-  RouteArgs ra{};
-  ra.rows = rows;
-  ra.vm = {(const Ins*)a->code.p, (const uint64_t*)a->konst.p};
-  ra.pat = rt.pa;
-  // ts_order 0: the owners run the order-tolerant path, which needs every
-  // B-stream row (a g-failing B expires partials, App. A.3), so no B is
-  // pushed down; sender and owners share the app's options
-  ra.pat.tolerant = (a->opt.ts_order == 0 && rt.order_sensitive) ? 1 : 0;
-  ra.world = world;
-  ra.wrw = wrw;
-  ra.tile_rows = (int32_t)tile_rows;
-  ra.seq0 = seq0;
-  ra.arena = (uint64_t*)a->route_arena.p;
-  ra.tcount = (uint32_t*)a->route_tcount.p;
-  ra.err = (unsigned int*)a->rerr.p;
-  ra.seg_cap = seg_cap;
-  ra.spill = (uint64_t*)sp.out;
-  ra.spill_cap = sp.cap;
-  ra.spill_counts = sp.counts;
-  {
-    LaunchTimer t(a, CEP_K_ROUTE, rs);
-    if (fast) {
-      CfRouteArgs ca{};
-      ca.r = ra;
-      ca.pref = rt.pref;
-      ca.ts_slot = -1;
-      for (int i = 0; i < rt.pref.n; ++i)
-        if (rows.cols.p[rt.pref.col[i]] == (const void*)rows.ts && rows.cols.t[rt.pref.col[i]] == T_LONG)
-          ca.ts_slot = i;
-      launch_cf_route(ca, ntiles, rs);
-      launch_route_collect(ra, ntiles, (uint32_t*)a->route_toffs.p,
-                           (unsigned long long*)a->route_dcount.p, (uint64_t*)rec_out, rs);
-    } else {
-      launch_route(ra, ntiles, rt.part_vm, (uint32_t*)a->route_toffs.p,
-                   (unsigned long long*)a->route_dcount.p, (uint64_t*)rec_out, rs);
-    }
-    if (seg_cap > 0) launch_route_pad(ra, (const unsigned long long*)a->route_dcount.p, (uint64_t*)rec_out, rs);
-  }
-  if (slot >= 0) hipEventRecord(a->hs[slot].free, rs);
-  if (seg_cap > 0) {
-    // the route's error bits travel in the segment headers (every owner
-    // reports them at its next flush); cleared behind the pad kernel
-    hipMemsetAsync(a->rerr.p, 0, 64, rs);
-    a->batches++;
-    return hipGetLastError() == hipSuccess ? CEP_OK : fail(a, CEP_E_DEVICE, "padded route launch failed");
-  }
-  // the per-owner counts: W words, read back on the route stream only (the
-  // all-to-all's split sizes are host values); the engine stream keeps going
-  std::vector<unsigned long long> dc(world);
-  unsigned int re = 0;
-  hipMemcpyAsync(dc.data(), a->route_dcount.p, world * 8, hipMemcpyDeviceToHost, rs);
-  hipMemcpyAsync(&re, a->rerr.p, 4, hipMemcpyDeviceToHost, rs);
-  if (hipStreamSynchronize(rs) != hipSuccess) return fail(a, CEP_E_DEVICE, "route failed");
-  int64_t total = 0;
-  for (int d = 0; d < world; ++d) {
-    counts_host[d] = (int64_t)dc[d];
-    total += (int64_t)dc[d];
-  }
-  if (total > b->n) return fail(a, CEP_E_DEVICE, "route produced more records than rows");
-  // the route kernels' own error word, read and cleared on the route stream
-  // (the walk's word belongs to cep_flush)
-  if (re) {
-    hipMemsetAsync(a->rerr.p, 0, 64, rs);
-    hipStreamSynchronize(rs);
-    return error_status(a, re);
-  }
-  a->batches++;
-  return CEP_OK;
-}
-
-int cep_route_batch(cep_app* a, const cep_batch* b, int world, int64_t seq0, void* rec_out,
-                    int64_t rec_cap, int64_t* counts_host) {
-  return route_batch(a, b, world, seq0, rec_out, rec_cap, counts_host, 0);
-}
-
-// A host batch is staged and routed on the engine stream; join that into the
-// route stream so cep_route_signal (which records on the route stream) also
-// orders a consumer after it (the padded routes read nothing back).
-static int route_join_host(cep_app* a, const cep_batch* b, int rc) {
-  if (rc != CEP_OK || !b || b->on_device) return rc;
-  if (hipEventRecord(a->r_host, a->stream) != hipSuccess ||
-      hipStreamWaitEvent(a->rstream, a->r_host, 0) != hipSuccess)
-    return fail(a, CEP_E_DEVICE, "route: stream join failed");
-  return rc;
-}
-
-int cep_route_batch_padded(cep_app* a, const cep_batch* b, int world, int64_t seq0, void* seg_out,
-                           int64_t seg_out_cap, int64_t seg_cap) {
-  if (seg_cap <= 0) return CEP_E_ARG;
-  return route_join_host(a, b, route_batch(a, b, world, seq0, seg_out, seg_out_cap, nullptr, seg_cap));
-}
-
-int cep_route_batch_padded_spill(cep_app* a, const cep_batch* b, int world, int64_t seq0, void* seg_out,
-                                 int64_t seg_out_cap, int64_t seg_cap, void* spill_out, int64_t spill_cap,
-                                 int64_t* spill_counts) {
-  if (seg_cap <= 0 || !spill_out || spill_cap < 0 || !spill_counts) return CEP_E_ARG;
-  SpillArgs sp;
-  sp.out = spill_out;
-  sp.cap = spill_cap;
-  sp.counts = spill_counts;
-  return route_join_host(a, b, route_batch(a, b, world, seq0, seg_out, seg_out_cap, nullptr, seg_cap, sp));
-}
-
-// Row shuffle plan: per input handle the owner key column (-1: any owner,
-// the stream feeds stateless filters only; -2: no query reads it).  Every
-// query that keeps per-key state must key each stream it reads on one
-// attribute, the same for all such queries; the shipped streams must share
-// one column layout (the owner unpacks them into one multi-stream batch).
-static int row_route_plan(cep_app* a, int32_t (&kc)[8], int* layout) {
-  const CompiledApp& app = a->app;
-  const int ni = (int)app.inputs.size();
-  if (ni > 8) return fail(a, CEP_E_UNSUPPORTED, "row shuffle supports at most 8 input streams");
-  if (!app.tables.empty()) return fail(a, CEP_E_UNSUPPORTED, kTableShuffle);
-  if (!a->joins.empty())
-    return fail(a, CEP_E_UNSUPPORTED, "row shuffle of an app that holds a join is not supported: its windows are "
-                                      "global, not per key");
-  for (int i = 0; i < 8; ++i) kc[i] = -2;
-  auto need = [&](int s, int col) -> int {
-    if (s < 0 || s >= ni) return CEP_OK;
-    if (col < 0) return fail(a, CEP_E_UNSUPPORTED, "row shuffle: query state on stream " + app.inputs[s].id +
-                                                     " is not keyed (needs `partition with` or group by)");
-    if (kc[s] >= 0 && kc[s] != col)
-      return fail(a, CEP_E_UNSUPPORTED, "row shuffle: stream " + app.inputs[s].id + " is keyed on two attributes");
-    kc[s] = col;
-    return CEP_OK;
-  };
-  for (auto& q : app.queries) {
-    int rc = CEP_OK;
-    if (q.kind == Q_FILTER) {
-      if (q.in_stream >= 0 && kc[q.in_stream] == -2) kc[q.in_stream] = -1;
-      continue;
-    }
-    if (q.kind == Q_AGG) {
-      rc = need(q.in_stream, q.key_col);
-    } else if (q.nfa) {
-      for (auto& st : q.nstates) {
-        rc = need(st.stream, st.stream >= 0 && st.stream < (int)q.key_col_s.size() ? q.key_col_s[st.stream] : -1);
-        if (rc) break;
-      }
-    } else {
-      rc = need(q.a_stream, q.key_col_a);
-      if (!rc) rc = need(q.b_stream, q.key_col_b);
-    }
-    if (rc) return rc;
-  }
-  // a keyed stream also read by a filter keeps its key (filters are stateless)
-  *layout = -1;
-  for (int s = 0; s < ni; ++s) {
-    if (kc[s] == -2) continue;
-    if (*layout < 0) {
-      *layout = s;
-      continue;
-    }
-    const auto& x = app.inputs[*layout].attrs;
-    const auto& y = app.inputs[s].attrs;
-    bool same = x.size() == y.size();
-    for (size_t c = 0; same && c < x.size(); ++c) same = x[c].type == y[c].type;
-    if (!same)
-      return fail(a, CEP_E_UNSUPPORTED, "row shuffle: streams " + app.inputs[*layout].id + " and " +
-                                            app.inputs[s].id + " have different column types");
-  }
-  if (*layout < 0) return fail(a, CEP_E_UNSUPPORTED, "row shuffle: no query reads any input stream");
-  return CEP_OK;
-}
-
-int cep_send_records(cep_app* a, const void* recs, int64_t n, int64_t events_represented) {
-  if (!a || (n > 0 && !recs) || n < 0) return CEP_E_ARG;
-  if (!a->enabled) return CEP_OK;
-  if (a->pats.size() != 1 || a->app.queries.size() != 1)
-    return fail(a, CEP_E_UNSUPPORTED, "records need an app with exactly one keyed pattern");
-  a->events_in += events_represented;
-  if (n == 0) return CEP_OK;
-  PatternRT& rt = a->pats[0];
-  RowsArgs rows{};
-  rows.n = n;
-  rows.row0 = 0;
-  rows.input = rt.pa.a_stream;
-  a->batches++;
-  return run_pattern(a, rt, rows, (const uint64_t*)recs, rt.pa.rec_words + 1);
-}
-
-int cep_send_records_padded(cep_app* a, const void* segs, int world, int64_t seg_cap,
-                            int64_t events_represented) {
-  if (!a || !segs || world <= 0 || world > kMaxWorld || seg_cap <= 0) return CEP_E_ARG;
-  if (!a->enabled) return CEP_OK;
-  if (a->pats.size() != 1 || a->app.queries.size() != 1)
-    return fail(a, CEP_E_UNSUPPORTED, "records need an app with exactly one keyed pattern");
-  a->events_in += events_represented;
-  PatternRT& rt = a->pats[0];
-  const int wrw = rt.pa.rec_words + 1;
-  // the headers' counts / error bits -> this engine's error word (reported
-  // by the next flush); the null records flow through the partitions, which
-  // skip role-0 records, so no count is read back here
-  launch_route_check((const uint64_t*)segs, world, seg_cap, wrw, 0, (unsigned int*)a->err.p, a->stream);
-  RowsArgs rows{};
-  rows.n = (int64_t)world * (1 + seg_cap);
-  rows.row0 = 0;
-  rows.input = rt.pa.a_stream;
-  a->batches++;
-  return run_pattern(a, rt, rows, (const uint64_t*)segs, wrw);
-}
-
-int cep_row_words(cep_app* a) {
-  if (!a) return -CEP_E_ARG;
-  int32_t kc[8];
-  int layout;
-  const int rc = row_route_plan(a, kc, &layout);
-  if (rc) return -rc;
-  return 3 + (int)a->app.inputs[layout].attrs.size();
-}
-
-// seg_cap == 0: owner-contiguous rows, counts read back (cep_route_rows);
-// seg_cap > 0: padded owner segments, counts in-band (cep_route_rows_padded).
-static int route_rows(cep_app* a, const cep_batch* b, int world, int64_t seq0, void* rec_out, int64_t rec_cap,
-                      int64_t* counts_host, int64_t seg_cap, const SpillArgs& sp = SpillArgs()) {
-  if (!a || !b || world <= 0 || seg_cap < 0 || (seg_cap == 0 && !counts_host)) return CEP_E_ARG;
-  if (world > kMaxWorld) return fail(a, CEP_E_ARG, "world exceeds " + std::to_string(kMaxWorld));
-  if (!a->app.derived.empty())
-    return fail(a, CEP_E_UNSUPPORTED, "row shuffle of an app with query chaining (derived streams) is not supported: "
-                                      "the sender needs the key in source columns");
-  int32_t kc[8];
-  int layout;
-  int rc = row_route_plan(a, kc, &layout);
-  if (rc) return rc;
-  if (seg_cap == 0) {
-    for (int d = 0; d < world; ++d) counts_host[d] = 0;
-    if (b->n == 0) return CEP_OK;
-    if (!rec_out || rec_cap < b->n)
-      return fail(a, CEP_E_ARG, "rec_out must hold at least n rows (" + std::to_string(b->n) + ")");
-  } else {
-    if (b->n == 0) return fail(a, CEP_E_ARG, "padded row shuffle needs a non-empty batch");
-    if (!rec_out || rec_cap < (int64_t)world * (1 + seg_cap))
-      return fail(a, CEP_E_ARG, "seg_out must hold world * (1 + seg_cap) rows");
-  }
-  if (b->stream) {
-    // a multi-stream batch needs one layout for all its streams (batch_rows)
-  } else if (kc[b->input] != -2) {
-    const auto& x = a->app.inputs[layout].attrs;
-    const auto& y = a->app.inputs[b->input].attrs;
-    bool same = x.size() == y.size();
-    for (size_t c = 0; same && c < x.size(); ++c) same = x[c].type == y[c].type;
-    if (!same) return fail(a, CEP_E_UNSUPPORTED, "row shuffle: batch stream layout differs");
-  }
-  RowsArgs rows{};
-  int slot;
-  bool direct;
-  rc = batch_rows(a, b, &rows, &slot, &direct);
-  if (rc) return rc;
-  const int64_t tile_rows = kPartThreads * kPartItems;
-  const int64_t ntiles = (b->n + tile_rows - 1) / tile_rows;
-  const int wrw = 3 + rows.cols.n;
-  hipStream_t rs = b->on_device ? a->rstream : a->stream;
-  if (!dev_ensure(&a->route_arena, (size_t)ntiles * tile_rows * wrw * 8, rs, false) ||
-      !dev_ensure(&a->route_tcount, (size_t)ntiles * world * 4, rs, false) ||
-      !dev_ensure(&a->route_toffs, (size_t)ntiles * world * 4, rs, false) ||
-      !dev_ensure(&a->route_dcount, (size_t)world * 8, rs, false))
-    return fail(a, CEP_E_DEVICE, "out of device memory (route arena)");
-  RowRouteArgs ra{};
-  ra.rows = rows;
-  ra.world = world;
-  ra.wrw = wrw;
-  ra.tile_rows = (int32_t)tile_rows;
-  ra.seq0 = seq0;
-  for (int i = 0; i < 8; ++i) ra.key_col_s[i] = kc[i];
-  ra.arena = (uint64_t*)a->route_arena.p;
-  ra.tcount = (uint32_t*)a->route_tcount.p;
-  ra.err = (unsigned int*)a->rerr.p;
-  ra.seg_cap = seg_cap;
-  ra.spill = (uint64_t*)sp.out;
-  ra.spill_cap = sp.cap;
-  ra.spill_counts = sp.counts;
-  {
-    LaunchTimer t(a, CEP_K_ROUTE, rs);
-    launch_route_rows(ra, ntiles, (uint32_t*)a->route_toffs.p, (unsigned long long*)a->route_dcount.p,
-                      (uint64_t*)rec_out, rs);
-  }
-  if (slot >= 0) hipEventRecord(a->hs[slot].free, rs);
-  if (seg_cap > 0) {   // nothing read back: the error bits travel in the headers
-    hipMemsetAsync(a->rerr.p, 0, 64, rs);
-    a->batches++;
-    return hipGetLastError() == hipSuccess ? CEP_OK : fail(a, CEP_E_DEVICE, "padded row route launch failed");
-  }
-  std::vector<unsigned long long> dc(world);
-  unsigned int re = 0;
-  hipMemcpyAsync(dc.data(), a->route_dcount.p, world * 8, hipMemcpyDeviceToHost, rs);
-  hipMemcpyAsync(&re, a->rerr.p, 4, hipMemcpyDeviceToHost, rs);
-  if (hipStreamSynchronize(rs) != hipSuccess) return fail(a, CEP_E_DEVICE, "row route failed");
-  int64_t total = 0;
-  for (int d = 0; d < world; ++d) {
-    counts_host[d] = (int64_t)dc[d];
-    total += (int64_t)dc[d];
-  }
-  if (total > b->n) return fail(a, CEP_E_DEVICE, "route produced more rows than the batch");
-  if (re) {   // the route kernels' own error word (route stream)
-    hipMemsetAsync(a->rerr.p, 0, 64, rs);
-    hipStreamSynchronize(rs);
-    return error_status(a, re);
-  }
-  a->batches++;
-  return CEP_OK;
-}
-
-int cep_route_rows(cep_app* a, const cep_batch* b, int world, int64_t seq0, void* rec_out, int64_t rec_cap,
-                   int64_t* counts_host) {
-  return route_rows(a, b, world, seq0, rec_out, rec_cap, counts_host, 0);
-}
-
-int cep_route_rows_padded(cep_app* a, const cep_batch* b, int world, int64_t seq0, void* seg_out,
-                          int64_t seg_out_cap, int64_t seg_cap) {
-  if (seg_cap <= 0) return CEP_E_ARG;
-  return route_join_host(a, b, route_rows(a, b, world, seq0, seg_out, seg_out_cap, nullptr, seg_cap));
-}
-
-int cep_route_rows_padded_spill(cep_app* a, const cep_batch* b, int world, int64_t seq0, void* seg_out,
-                                int64_t seg_out_cap, int64_t seg_cap, void* spill_out, int64_t spill_cap,
-                                int64_t* spill_counts) {
-  if (seg_cap <= 0 || !spill_out || spill_cap < 0 || !spill_counts) return CEP_E_ARG;
-  SpillArgs sp;
-  sp.out = spill_out;
-  sp.cap = spill_cap;
-  sp.counts = spill_counts;
-  return route_join_host(a, b, route_rows(a, b, world, seq0, seg_out, seg_out_cap, nullptr, seg_cap, sp));
-}
-
-int cep_send_rows_padded(cep_app* a, const void* segs, int world, int64_t seg_cap, int64_t events_represented) {
-  if (!a || !segs || world <= 0 || world > kMaxWorld || seg_cap <= 0) return CEP_E_ARG;
-  if (!a->enabled) return CEP_OK;
-  const int w = cep_row_words(a);
-  if (w < 0) return -w;
-  // headers -> this engine's error word; header and null rows carry stream
-  // handle kRowNullStream, which no query reads
-  launch_route_check((const uint64_t*)segs, world, seg_cap, w, 1, (unsigned int*)a->err.p, a->stream);
-  return cep_send_rows(a, segs, (int64_t)world * (1 + seg_cap), events_represented);
-}
-
-int cep_send_rows(cep_app* a, const void* recs, int64_t n, int64_t events_represented) {
-  if (!a || (n > 0 && !recs) || n < 0) return CEP_E_ARG;
-  if (!a->enabled) return CEP_OK;
-  int32_t kc[8];
-  int layout;
-  int rc = row_route_plan(a, kc, &layout);
-  if (rc) return rc;
-  a->events_in += events_represented;
-  if (n == 0) return CEP_OK;
-  const StreamSchema& sd = a->app.inputs[layout];
-  const int nc = (int)sd.attrs.size();
-  RowUnpackArgs ua{};
-  ua.recs = (const uint64_t*)recs;
-  ua.n = n;
-  ua.wrw = 3 + nc;
-  ua.ncols = nc;
-  bool ok = true;
-  for (int c = 0; c < nc && ok; ++c) {
-    ok = dev_ensure(&a->rr_col[c], (size_t)n * type_width(sd.attrs[c].type) + 16, a->stream, false);
-    ua.col[c] = a->rr_col[c].p;
-    ua.type[c] = sd.attrs[c].type;
-  }
-  ok = ok && dev_ensure(&a->rr_ts, (size_t)n * 8, a->stream, false) &&
-       dev_ensure(&a->rr_stream, (size_t)n + 16, a->stream, false) &&
-       dev_ensure(&a->rr_seq, (size_t)n * 8, a->stream, false);
-  if (!ok) return fail(a, CEP_E_DEVICE, "out of device memory (received rows)");
-  ua.ts = (int64_t*)a->rr_ts.p;
-  ua.stream = (uint8_t*)a->rr_stream.p;
-  ua.seq = (int64_t*)a->rr_seq.p;
-  {
-    LaunchTimer t(a, CEP_K_OTHER);
-    launch_unpack_rows(ua, a->stream);
-  }
-  RowsArgs rows{};
-  rows.cols.n = nc;
-  for (int c = 0; c < nc; ++c) {
-    rows.cols.p[c] = ua.col[c];
-    rows.cols.t[c] = sd.attrs[c].type;
-  }
-  rows.ts = ua.ts;
-  rows.stream = ua.stream;
-  rows.input = layout;
-  rows.row0 = 0;
-  rows.n = n;
-  rows.seq0 = 0;
-  rows.seq = ua.seq;
-  rows.prev_ts = INT64_MIN;
-  a->last_ts = INT64_MIN;
-  a->batches++;
-  return send_device_rows(a, rows);
-}
 
 int cep_plan_partition_keys(const char* plan, const char* stream_id, char* buf, size_t len) {
   if (!plan || !stream_id || !buf || !len) return CEP_E_ARG;
