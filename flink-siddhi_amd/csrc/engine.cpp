@@ -257,6 +257,7 @@ int create_runtime(cep_app* a) {
       p.slot_words = 2 + p.ncap;
       p.key_words = 1 + S * p.slot_words;
       p.stream_mask = 0;
+      p.st_logic = 0;
       for (int j = 0; j < p.nstates; ++j) {
         const auto& st = q.nstates[j];
         p.st_stream[j] = st.stream;
@@ -264,6 +265,7 @@ int create_runtime(cep_app* a) {
         p.st_max[j] = st.max_count;
         p.st_raw[j] = st.raw.off;
         p.st_walk[j] = st.walk.off;
+        p.st_logic |= st.logic << (2 * j);
         p.stream_mask |= 1 << st.stream;
       }
       for (int j = 0; j < p.nstates; ++j) {

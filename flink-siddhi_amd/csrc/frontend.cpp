@@ -197,6 +197,7 @@ struct State {
   std::string alias, stream;
   ExprP cond;
   int min_count = 1, max_count = 1;
+  int logic = 0;   // first side of a logical group: 1 `and` / 2 `or` with the next state
 };
 
 struct SelItem {
@@ -415,8 +416,44 @@ class Parser {
   }
 
   bool is_state_start() const {
+    size_t k = 0;
     if (peek().k == TK_KW && peek().v == "every") return true;
-    return peek().k == TK_ID && peek(1).k == TK_OP && peek(1).v == "=";
+    if (peek().k == TK_OP && peek().v == "(") k = 1;   // a parenthesised logical group
+    if (peek(k).k == TK_KW && peek(k).v == "not") return true;   // an absent state (refused by name)
+    if (k && peek(k).k == TK_KW && peek(k).v == "every") return true;
+    return peek(k).k == TK_ID && peek(k + 1).k == TK_OP && peek(k + 1).v == "=";
+  }
+
+  // One position of a pattern / sequence: a state, or a logical group
+  // `x=X[f] and y=Y[g]` / `x=X[f] or y=Y[g]` (parentheses optional), which
+  // becomes two consecutive states, the first carrying the operator.
+  void position(std::vector<State>* states) {
+    auto absent = [&]() {
+      if (peek().k == TK_KW && peek().v == "not")
+        fail(CEP_E_UNSUPPORTED, "absent pattern states (not ...) are not supported");
+    };
+    auto logical = [&]() { return peek().k == TK_KW && (peek().v == "and" || peek().v == "or"); };
+    const bool every = peek().k == TK_KW && peek().v == "every" && peek(1).k == TK_OP && peek(1).v == "(";
+    if (every) next();
+    const bool paren = accept(TK_OP, "(");
+    absent();
+    State s = state();
+    s.every = s.every || every;
+    if (!logical()) {
+      if (paren) fail(CEP_E_PARSE, "'and' or 'or' expected in a parenthesised pattern group");
+      states->push_back(s);
+      return;
+    }
+    const std::string op = next().v;
+    absent();
+    State t = state();
+    if (logical())
+      fail(CEP_E_UNSUPPORTED, peek().v == op ? "logical pattern states of more than two sides are not supported"
+                                             : "logical pattern states mixing 'and' and 'or' are not supported");
+    if (paren) expect(TK_OP, ")");
+    s.logic = op == "and" ? 1 : 2;
+    states->push_back(s);
+    states->push_back(t);
   }
 
   QueryAst query() {
@@ -455,13 +492,13 @@ class Parser {
       }
     } else {
       q.single = false;
-      q.states.push_back(state());
+      position(&q.states);
       std::string sep;
       while (peek().k == TK_OP && (peek().v == "->" || peek().v == ",")) {
         std::string s = next().v;
         if (sep.empty()) sep = s;
         else if (sep != s) fail(CEP_E_UNSUPPORTED, "mixed '->' and ',' is not supported");
-        q.states.push_back(state());
+        position(&q.states);
       }
       q.sequence = (sep == ",");
       if (accept(TK_KW, "within")) q.within = time_const();
@@ -1608,7 +1645,8 @@ void compile_nfa(CompiledApp* app, QueryAst& q) {
     ns.stream = app->input_index(q.states[j].stream);
     ns.min_count = q.states[j].min_count;
     ns.max_count = q.states[j].max_count;
-    ns.terms.n = 0;   // no condition: always true
+    ns.logic = q.states[j].logic;
+    ns.terms.n = 0;  // no condition: always true
     if (q.states[j].cond) {
       ns.terms.n = -1;
       if (self_only(q.states[j].cond, j)) {
@@ -1661,9 +1699,43 @@ bool refs_alias(const ExprP& e, const std::string& alias) {
   return false;
 }
 
+// Logical groups (`x=X[f] and y=Y[g]`, `... or ...`: states j, j + 1 with
+// states[j].logic set): the forms refused by name.  Returns
+// whether the query has one.
+bool check_logical(const QueryAst& q) {
+  bool any = false;
+  const int n = (int)q.states.size();
+  for (int j = 0; j + 1 < n; ++j) {
+    if (!q.states[j].logic) continue;
+    any = true;
+    const State& x = q.states[j];
+    const State& y = q.states[j + 1];
+    if (q.sequence) fail(CEP_E_UNSUPPORTED, "logical states (and / or) in a sequence are not supported");
+    if (j == 0) fail(CEP_E_UNSUPPORTED, "a logical group (and / or) as the first pattern position is not supported");
+    if (x.every || y.every) fail(CEP_E_UNSUPPORTED, "'every' on a side of a logical pattern state is not supported");
+    if (x.min_count != 1 || x.max_count != 1 || y.min_count != 1 || y.max_count != 1)
+      fail(CEP_E_UNSUPPORTED, "a count suffix on a side of a logical pattern state is not supported");
+    if (x.stream == y.stream)
+      fail(CEP_E_UNSUPPORTED, "a logical pattern state whose two sides read the same stream (" + x.stream +
+                                  ") is not supported");
+    if ((!y.alias.empty() && refs_alias(x.cond, y.alias)) || (!x.alias.empty() && refs_alias(y.cond, x.alias)))
+      fail(CEP_E_UNSUPPORTED, "a side of a logical pattern state whose condition reads its partner's capture "
+                              "is not supported");
+    if (x.logic == 2)
+      for (int k = j + 2; k < n; ++k)
+        for (const State* s : {&x, &y})
+          if (!s->alias.empty() && refs_alias(q.states[k].cond, s->alias))
+            fail(CEP_E_UNSUPPORTED, "a condition reading a capture of an 'or' side (" + s->alias +
+                                        ", which may be null) is not supported");
+    ++j;
+  }
+  return any;
+}
+
 void compile_pattern(CompiledApp* app, QueryAst& q) {
   bool counts = false;
   for (auto& s : q.states) counts |= s.min_count != 1 || s.max_count != 1;
+  if (check_logical(q)) return compile_nfa(app, q);
   if (q.sequence || q.states.size() != 2 || counts) return compile_nfa(app, q);
   // s2's condition reads s1: the N-state walk (its pending lists continue in
   // the pending pool, so no key runs out of slots); CEP_PAIR_WALK=1 keeps the

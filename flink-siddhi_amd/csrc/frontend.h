@@ -100,6 +100,7 @@ struct Query {
   struct NState {
     int stream = -1;
     int min_count = 1, max_count = 1;   // max -1: unbounded
+    int logic = 0;   // first side of a logical position: 1 `and` / 2 `or` with the next state
     Prog raw;      // condition over the event's own columns (partition pass)
     Prog walk;     // condition reading earlier states (walk: LDCOL word, LDCAP capture)
     TermList terms;   // interpreter-free form of raw (n = 0: no condition, -1: not expressible)

@@ -156,6 +156,9 @@ struct PatternArgs {
   int32_t st_tail_opt[kMaxStates]; // every state after j is optional (min 0)
   int32_t key_col_s[8];            // partition key column per input handle
   int32_t cap_state[kMaxCaps], cap_index[kMaxCaps], cap_word[kMaxCaps];
+  int32_t st_logic;                // logical positions, 2 bits per state j: 0 none, 1 `and` / 2 `or` with
+                                   // state j + 1 (set on the first side only; the partial's state word
+                                   // then holds j | filled sides << 8); 0: the plan has none
   uint64_t cap_null[kMaxCaps];      // a capture of a state that never matched: 0, or id -1 (null) for STRING
 };
 

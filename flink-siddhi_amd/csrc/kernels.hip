@@ -1390,7 +1390,11 @@ __device__ uint32_t agg_key(const WalkArgs& a, WalkLds& L, uint64_t* R, int k, i
 // App. A.3-A.5).  Patterns: a partial advances when the event is on its next
 // state's stream and the condition holds (else it stays), expired partials
 // are dropped, advanced partials move behind the ones that stayed, a start
-// event appends a new partial.  Sequences: every event of the query's streams
+// event appends a new partial.  A logical position (`B and C`, `B or C`:
+// st_logic) is two states sharing one place in the chain; a
+// pattern's state word has no count, so its bits 8-9 say which sides are
+// filled, and a half-filled `and` partial keeps its place in the list.
+// Sequences: every event of the query's streams
 // either advances a partial (staying in a count state, or moving to a later
 // state skipping optional ones) or discards it.  Matches reserve output rows
 // one by one (a lane's rows of one event stay in creation order).
@@ -1449,7 +1453,9 @@ __device__ __forceinline__ void nfa_emit(const WalkArgs& a, uint64_t* R, const u
   emit_row<kVm>(a, R, env, key_value(p, kl), rec_seq(rec, seq_base), pos);
 }
 
-template <bool kVm>
+// kLogic: the plan has a logical position (PatternArgs::st_logic != 0); plans
+// without one run the instance that has no trace of the transition.
+template <bool kVm, bool kLogic>
 __device__ __noinline__ void nfa_key(const WalkArgs& a, WalkLds& L, uint64_t* R, int k, int bucket, int kpb,
                         int64_t ts_base, int64_t seq_base) {
   const PatternArgs& p = a.pat;
@@ -1530,21 +1536,41 @@ __device__ __noinline__ void nfa_key(const WalkArgs& a, WalkLds& L, uint64_t* R,
         uint64_t* si = NSLOT(i);
         // a 2-state pattern's partials all wait on state 1 (its at-rest slots
         // do not hold the state word)
-        const int j = p.nfa_pair ? 1 : (int)(si[st] & 0xffu);
+        int j = p.nfa_pair ? 1 : (int)(si[st] & 0xffu);
+        // logical position: states j, j + 1 are its two sides,
+        // bits 8-9 of the state word say which are filled; the event counts
+        // for the side of its stream, if that side is still open
+        const int lg = (!kLogic || p.nfa_pair) ? 0 : (p.st_logic >> (2 * j)) & 3;
+        uint32_t filled = 0;
+        int nxt = j + 1;
+        if (lg) {
+          filled = (uint32_t)(si[st] >> 8) & 3u;
+          const int side = p.st_stream[j] == stream ? 0 : 1;
+          if ((filled >> side) & 1u) { copy_slot(m++, i); continue; }
+          nxt = j + 2;
+          j += side;
+          filled |= 1u << side;
+        }
         if (p.st_stream[j] != stream) { copy_slot(m++, i); continue; }
         if (p.within >= 0) {
           const int64_t d = ts - (int64_t)si[0];
           if ((d < 0 ? -d : d) > p.within) continue;   // expired: dropped
         }
         if (!nfa_cond<kVm>(a, R, j, role, si, st, rec, ts_base)) { copy_slot(m++, i); continue; }
-        if (j + 1 == N) {
+        if (lg == 1 && filled != 3u) {   // `and`: waits for its partner, in place
+          nfa_collect(p, si, st, j, 1, rec);
+          si[st] = (uint64_t)(uint32_t)(nxt - 2) | ((uint64_t)filled << 8);
+          copy_slot(m++, i);
+          continue;
+        }
+        if (nxt == N) {
           nfa_collect(p, si, st, j, 1, rec);
           nfa_emit<kVm>(a, R, si, st, rec, ts_base, seq_base, kl);   // consumed
           continue;
         }
         copy_slot(CAP + nf, i);
-        nfa_collect(p, NSLOT(CAP + nf), st, j + 1 - 1, 1, rec);
-        NSLOT(CAP + nf)[st] = (uint64_t)(j + 1);
+        nfa_collect(p, NSLOT(CAP + nf), st, j, 1, rec);
+        NSLOT(CAP + nf)[st] = (uint64_t)nxt;
         ++nf;
       }
       if (p.st_stream[0] == stream && (p.every || !started) &&
@@ -1858,8 +1884,13 @@ __global__ __launch_bounds__(kWalkThreads) void k_walk(WalkArgs a) {
     if (nfa) {
       // ---- N-state pattern / sequence: one NFA lane per key -----------------
       if constexpr (kVm) {
-        for (int k = tid; k < kpb; k += kWalkThreads)
-          if (L.kstart[k + 1] > L.kstart[k]) nfa_key<kVm>(a, L, R, k, bucket, kpb, ts_base, seq_base);
+        if (!p.st_logic) {
+          for (int k = tid; k < kpb; k += kWalkThreads)
+            if (L.kstart[k + 1] > L.kstart[k]) nfa_key<kVm, false>(a, L, R, k, bucket, kpb, ts_base, seq_base);
+        } else {
+          for (int k = tid; k < kpb; k += kWalkThreads)
+            if (L.kstart[k + 1] > L.kstart[k]) nfa_key<kVm, true>(a, L, R, k, bucket, kpb, ts_base, seq_base);
+        }
       }
     } else if (kVm && p.agg_mode) {
       // ---- group-by / having: one lane per group, count pass + emit pass ----

@@ -93,6 +93,7 @@ static bool mq_candidate(const cep_app* a, const Query& q, MqNeeds* nd) {
   if ((int)q.ncaps.size() > kMqMaxCaps || (int)q.select.size() > kMqMaxSel) return false;
   for (int j = 0; j < n; ++j) {
     const auto& st = q.nstates[j];
+    if (st.logic) return false;   // logical states: the stand-alone walk only
     if (j > 0 && st.stream == q.nstates[0].stream) return false;   // one live partial per key
     if (st.walk.valid() || st.terms.n < 0 || st.min_count > 254 || st.max_count > 254) return false;
     const int col = st.stream < (int)q.key_col_s.size() ? q.key_col_s[st.stream] : -1;

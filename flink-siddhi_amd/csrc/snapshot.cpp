@@ -369,6 +369,17 @@ uint64_t plan_hash(const CompiledApp& app) {
       mix(q.tab_set, sizeof(q.tab_set));
     }
   }
+  // logical pattern states: `A -> B and C` and `A -> B or C` compile to the
+  // same code (plans without one hash as before)
+  for (size_t qi = 0; qi < app.queries.size(); ++qi) {
+    const Query& q = app.queries[qi];
+    bool any = false;
+    for (auto& st : q.nstates) any = any || st.logic != 0;
+    if (!any) continue;
+    const int64_t w[2] = {-6, (int64_t)qi};
+    mix(w, sizeof(w));
+    for (auto& st : q.nstates) mix(&st.logic, sizeof(st.logic));
+  }
   // query chaining (plans without derived streams hash as before)
   for (auto& d : app.derived) {
     const int64_t w[5] = {-1, d.stream, d.producer, d.source, d.stage};

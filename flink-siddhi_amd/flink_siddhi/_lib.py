@@ -55,7 +55,10 @@ class DuplicatedStreamException(SiddhiError):
 
 
 class UnsupportedPlanException(SiddhiError):
-    """Valid SiddhiQL outside the device subset: outer joins, tables without a
+    """Valid SiddhiQL outside the device subset: absent pattern states (`not X
+    for t`) and the logical pattern states the walk does not take (a group as
+    the first position, in a sequence, of three sides, on one stream, reading
+    its partner or read as an `or` side by a later condition), outer joins, tables without a
     primary key or addressed by anything but that key, stream functions, and every window but the sliding `#window.length(N)` /
     `#window.time(T)` aggregates whose window instance is the aggregate group
     (batch / external-time windows, a length window shared by several groups,

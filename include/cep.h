@@ -24,6 +24,22 @@
  * and valid only during the callback.  Snapshot buffers are engine-allocated
  * and released with cep_free().
  *
+ * Pattern queries: `from [every] a=A[f] -> P -> ... [within W] select ...`,
+ * at most 6 elementary states.  A position P after the first is a state
+ * `x=X[g]` or a logical group of two states on different streams, `x=X[g]
+ * and y=Y[h]` or `x=X[g] or y=Y[h]`, with or without parentheses.  `and`: the
+ * first matching event of each side is its capture, in either order, and the
+ * position is complete when both sides are filled; `or`: the first matching
+ * event of either side completes it and the other side's captures stay null
+ * (below).  `within` is checked when an event of a still open side arrives.
+ * A side's condition may read earlier positions' captures (upstream Siddhi
+ * 4.x semantics).  CEP_E_UNSUPPORTED (the message names
+ * the construct): a group as the first position or in a sequence (`,`), more
+ * than two sides or `and` mixed with `or`, two sides on one stream, a side
+ * reading its partner's capture, a later condition reading a capture of an
+ * `or` side, a count suffix or `every` on a side, and absent states (`not X
+ * for t`, `... and not X`).
+ *
  * Window queries: a single-stream query may put one sliding window after its
  * filter, `from S[f]#window.length(N) ...` (N rows, 1 <= N <= 255) or
  * `from S[f]#window.time(T) ...` (T in ms or with units, >= 1; the clock is
@@ -272,8 +288,9 @@ typedef struct {
 /* Output rows, columnar, in emission order (see cep_options.ordered_output).
  *
  * Null: a select item that reads a capture of a pattern / sequence state that
- * never matched (an optional state `?`, `*`, `<0:n>` the match skipped, or
- * sK[n] of a state that collected fewer than n + 1 events) is null in Siddhi.
+ * never matched (an optional state `?`, `*`, `<0:n>` the match skipped,
+ * sK[n] of a state that collected fewer than n + 1 events, or the side of an
+ * `or` group that did not complete it) is null in Siddhi.
  * Columns carry no validity bits; in an output row such an item is
  *   - 0 for INT, LONG, FLOAT, DOUBLE (all bits zero) and false for BOOL,
  *   - dictionary id -1 for STRING (no string has it: cep_dict_lookup(-1) is
