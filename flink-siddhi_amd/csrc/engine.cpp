@@ -164,7 +164,8 @@ int create_runtime(cep_app* a) {
     if (q.kind != Q_PATTERN && q.kind != Q_AGG) continue;
     if (a->in_mq[qi]) continue;   // served by a multi-query group
     const bool agg = q.kind == Q_AGG;
-    const bool win = agg && q.win_kind != WIN_NONE;
+    const bool batch = agg && win_is_batch(q.win_kind);
+    const bool win = agg && q.win_kind != WIN_NONE && !batch;
     // group-by state: one slot of (accumulator, count) pairs per group (a
     // window query: one slot of accumulators + the ring, kernels.h WinArgs)
     const int S = agg ? 1 : a->opt.pending_slots;
@@ -231,6 +232,27 @@ int create_runtime(cep_app* a) {
     p.rec_words = 2 + std::max(p.nrec_a, p.nrec_b);
     p.slot_words = agg ? 2 * (int)q.aggs.size() : 2 + p.ncap;
     if (win) p.slot_words = (int)q.aggs.size() + rt.win.ring * rt.win.entry_words;
+    if (batch) {
+      // one slot per key: the open batch, then the candidate (kernels.h BatchArgs)
+      BatchArgs& b = rt.bat;
+      const int nagg = (int)q.aggs.size();
+      const bool timed = q.win_kind == WIN_TIME_BATCH;
+      const bool hav = q.having.valid();
+      b.kind = q.win_kind;
+      b.param = q.win_param;
+      b.time_word = q.win_word;
+      int w = nagg + 1;
+      b.time_w = timed ? w : -1;
+      if (timed) w += 2;
+      b.cand_acc_w = hav ? w : -1;
+      if (hav) w += nagg + 1;
+      // the emitted row is the trigger itself only for lengthBatch without having
+      b.cand_w = (timed || hav) ? w : -1;
+      if (b.cand_w >= 0) w += 1 + p.nrec_a;
+      p.slot_words = w;
+      rt.win_vm = hav;
+      for (auto& it : q.select) rt.win_vm |= it.src == SRC_VM;
+    }
     p.key_words = 1 + S * p.slot_words;
     p.pending_slots = S;
     // case (c) relies on event-time order: the partition pass checks it
@@ -1281,6 +1303,27 @@ int run_pattern(cep_app* a, PatternRT& rt, const RowsArgs& rows_in, const uint64
       pipe.walked(b, a->stream);
       continue;
     }
+    if (rt.bat.kind != WIN_NONE) {
+      BatchArgs bw = rt.bat;
+      bw.vm = pa.vm;
+      bw.pat = pa.pat;
+      bw.recs = pa.recs;
+      bw.tile_off = pa.tile_off;
+      bw.ntiles = (int)ntiles;
+      bw.tile_rows = pa.tile_rows;
+      bw.chunk_base = wa.chunk_base;
+      bw.khdr = wa.khdr;
+      bw.kslot = wa.kslot;
+      bw.kstride = wa.kstride;
+      bw.out = wa.out;
+      bw.err = wa.err;
+      {
+        LaunchTimer t(a, CEP_K_AGG);
+        launch_batchwalk(bw, P, rt.win_vm, a->stream);
+      }
+      pipe.walked(b, a->stream);
+      continue;
+    }
     const bool pool = (q.nfa || pa.pat.nfa_pair) && rt.kext.p;
     if (pool) {
       wa.kext = (uint64_t*)rt.kext.p;
@@ -1861,7 +1904,7 @@ cep_app* cep::create_app(const char* plan, const cep_options* opt, const std::ve
   bool has_pattern = false, has_window = false;
   for (auto& q : a->app.queries) {
     has_pattern |= q.kind == Q_PATTERN;
-    has_window |= q.win_kind != WIN_NONE;
+    has_window |= q.win_kind == WIN_LENGTH || q.win_kind == WIN_TIME;   // (a batch window keeps no ring)
   }
   const int max_pending = (has_window && !has_pattern) ? kWinMaxRing : kMaxPending;
   if (a->opt.pending_slots <= 0 || a->opt.pending_slots > max_pending) {

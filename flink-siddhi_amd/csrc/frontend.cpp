@@ -210,8 +210,9 @@ struct QueryAst {
   bool sequence = false;
   std::string stream, alias;
   std::vector<ExprP> filters;
-  int win_kind = WIN_NONE;     // sliding window after the filters
-  int64_t win_param = 0;       // rows (length) / ms (time)
+  int win_kind = WIN_NONE;     // window after the filters (sliding, or a tumbling batch window)
+  int64_t win_param = 0;       // rows (length, lengthBatch) / ms (time, externalTimeBatch)
+  std::string win_attr;        // externalTimeBatch: the name of its time attribute
   std::string win_events;      // window queries: the 'insert <x> events' keyword ("" = none given)
   // windowed stream join: the second side and the `on` condition (null: none)
   bool join = false;
@@ -219,6 +220,7 @@ struct QueryAst {
   std::vector<ExprP> filters2;
   int win_kind2 = WIN_NONE;
   int64_t win_param2 = 0;
+  std::string win_attr2;
   ExprP on;
   std::vector<State> states;
   int64_t within = -1;
@@ -463,7 +465,7 @@ class Parser {
       fail(CEP_E_UNSUPPORTED, "inner streams (from #" + peek(1).v + ") are not supported");
     if (!is_state_start()) {
       q.single = true;
-      side(&q.stream, &q.alias, &q.filters, &q.win_kind, &q.win_param);
+      side(&q.stream, &q.alias, &q.filters, &q.win_kind, &q.win_param, &q.win_attr);
       // joins: inner joins of two windowed streams compile (compile_join);
       // every other join form is refused here by name
       auto word = [&](const char* w) { return peek().k == TK_ID && lower(peek().v) == w; };
@@ -480,7 +482,7 @@ class Parser {
         q.join = true;
         if (peek().k == TK_OP && peek().v == "#")
           fail(CEP_E_UNSUPPORTED, "inner streams (join #" + peek(1).v + ") are not supported");
-        side(&q.stream2, &q.alias2, &q.filters2, &q.win_kind2, &q.win_param2);
+        side(&q.stream2, &q.alias2, &q.filters2, &q.win_kind2, &q.win_param2, &q.win_attr2);
         if (peek().k == TK_KW && peek().v == "unidirectional")
           fail(CEP_E_UNSUPPORTED, (table_ids_.count(q.stream) || table_ids_.count(q.stream2))
                                       ? "a unidirectional join against a table is not supported"
@@ -575,7 +577,8 @@ class Parser {
   }
 
   // One input side: `Stream[filter]*[#window.x(..)] [as alias]`.
-  void side(std::string* stream, std::string* alias, std::vector<ExprP>* filters, int* win_kind, int64_t* win_param) {
+  void side(std::string* stream, std::string* alias, std::vector<ExprP>* filters, int* win_kind, int64_t* win_param,
+            std::string* win_attr) {
     *stream = ident();
     while (true) {
       if (accept(TK_OP, "[")) {
@@ -584,7 +587,7 @@ class Parser {
       } else if (peek().k == TK_OP && peek().v == "#") {
         if (*win_kind != WIN_NONE)
           fail(CEP_E_UNSUPPORTED, "a second window / stream function after #window is not supported");
-        window(win_kind, win_param);
+        window(win_kind, win_param, win_attr);
         if (peek().k == TK_OP && peek().v == "[")
           fail(CEP_E_UNSUPPORTED, "a filter after the window (#window.x(..)[f]) is not supported");
       } else {
@@ -594,8 +597,10 @@ class Parser {
     if (accept(TK_KW, "as")) *alias = ident();
   }
 
-  // '#window.length(N)' / '#window.time(T)'; every other '#...' is refused.
-  void window(int* kind, int64_t* param) {
+  // '#window.length(N)' / '#window.time(T)' and the tumbling
+  // '#window.lengthBatch(N)' / '#window.externalTimeBatch(c, T)'; every other
+  // '#...' is refused.
+  void window(int* kind, int64_t* param, std::string* attr) {
     expect(TK_OP, "#");
     Token t = next();
     if (!(t.k == TK_KW && t.v == "window")) {
@@ -607,25 +612,51 @@ class Parser {
     Token nt = next();
     if (nt.k != TK_ID && nt.k != TK_KW) fail(CEP_E_PARSE, "window name expected after '#window.'");
     const std::string name = nt.v;
-    if (name != "length" && name != "time")
-      fail(CEP_E_UNSUPPORTED, "#window." + name + " is not supported (only #window.length and #window.time)");
+    const bool ext = name == "externalTimeBatch";
+    if (name != "length" && name != "time" && name != "lengthBatch" && !ext)
+      fail(CEP_E_UNSUPPORTED, "#window." + name + " is not supported (only #window.length, #window.time, "
+                              "#window.lengthBatch and #window.externalTimeBatch)");
+    const bool timed = name == "time" || ext;
     expect(TK_OP, "(");
+    if (ext) {
+      // the time attribute, then the batch length; the optional start time,
+      // timeout and replace-timestamp arguments are refused
+      const bool named = peek().k == TK_ID || peek().k == TK_KW;
+      const std::string after = peek(1).v;
+      if (!named || peek(1).k != TK_OP || (after != "," && after != ")" && after != "."))
+        fail(CEP_E_PARSE, "#window.externalTimeBatch takes an attribute of the stream as its first argument, got '" +
+                              peek().v + "'");
+      *attr = next().v;
+      // S.c / e.c: kept as "qualifier.c"; the alias follows the window clause,
+      // so compile_single checks the qualifier against the stream and alias
+      if (accept(TK_OP, ".")) *attr += "." + ident();
+      if (!accept(TK_OP, ","))
+        fail(CEP_E_PARSE, "#window.externalTimeBatch takes an attribute and a constant time, got '" + peek().v + "'");
+    }
     int64_t v = -1;
-    if (peek().k == TK_NUM && peek(1).k == TK_OP && peek(1).v == ")") {
+    auto closes = [&](int k) { return peek(k).k == TK_OP && (peek(k).v == ")" || (ext && peek(k).v == ",")); };
+    if (peek().k == TK_NUM && closes(1)) {
       std::string n = next().v;
       while (!n.empty() && (n.back() == 'l' || n.back() == 'L')) n.pop_back();
       if (n.empty() || n.find_first_not_of("0123456789") != std::string::npos)
         fail(CEP_E_PARSE, "#window." + name + " takes an integer constant, got " + n);
+      // (the batch windows only: the sliding windows' handling of an over-long constant stays as it was)
+      if ((ext || name == "lengthBatch") && n.size() > 18) fail(CEP_E_PARSE, "#window." + name + " takes an integer constant, got " + n);
       v = std::stoll(n);
-    } else if (name == "time" && peek().k == TK_NUM && peek(1).k == TK_ID) {
+    } else if (timed && peek().k == TK_NUM && peek(1).k == TK_ID) {
       v = time_const();
     } else {
       fail(CEP_E_PARSE, "#window." + name + " takes one constant " +
-                            (name == "time" ? "time in ms or with units" : "row count") + ", got '" + peek().v + "'");
+                            (timed ? "time in ms or with units" : "row count") + ", got '" + peek().v + "'");
     }
+    if (ext && peek().k == TK_OP && peek().v == ",")
+      fail(CEP_E_UNSUPPORTED, "#window.externalTimeBatch with more than two arguments (start time, timeout, "
+                              "replace-timestamp) is not supported");
     expect(TK_OP, ")");
     if (v < 1) fail(CEP_E_PARSE, "#window." + name + " needs a constant >= 1");
-    *kind = name == "length" ? WIN_LENGTH : WIN_TIME;
+    if (name == "lengthBatch" && v > 2147483647LL)
+      fail(CEP_E_PARSE, "#window.lengthBatch needs a constant <= 2147483647");
+    *kind = name == "length" ? WIN_LENGTH : name == "time" ? WIN_TIME : ext ? WIN_TIME_BATCH : WIN_LENGTH_BATCH;
     *param = v;
   }
 
@@ -1356,6 +1387,11 @@ void lower_aggregation(CompiledApp* app, Query& q) {
   }
   for (auto& it : q.select) collect_cols(app, it.prog, &cols);
   collect_cols(app, q.having, &cols);
+  // #window.externalTimeBatch(c, T): the walk reads c from the record
+  if (q.win_col >= 0) {
+    if (std::find(cols.begin(), cols.end(), q.win_col) == cols.end()) cols.push_back(q.win_col);
+    q.win_word = (int)(std::find(cols.begin(), cols.end(), q.win_col) - cols.begin());
+  }
   if ((int)cols.size() > kMaxCaps) fail(CEP_E_UNSUPPORTED, "group-by query reads too many attributes");
   q.a_stream = q.in_stream;
   q.b_stream = -1;
@@ -1460,7 +1496,43 @@ void compile_single(CompiledApp* app, QueryAst& q) {
     out.group_cols.push_back(g->col);
   }
   bool agg = !out.aggs.empty();
-  if (q.win_kind != WIN_NONE) {
+  if (win_is_batch(q.win_kind)) {
+    // Tumbling windows: one window instance per partition key,
+    // one output row per closed batch.
+    const std::string wn = std::string("#window.") + win_name(q.win_kind);
+    if (q.win_kind == WIN_TIME_BATCH) {
+      std::string attr = q.win_attr;
+      const size_t dot = attr.find('.');
+      if (dot != std::string::npos) {
+        const std::string ref = attr.substr(0, dot);
+        attr = attr.substr(dot + 1);
+        if (ref != q.stream && (q.alias.empty() || ref != q.alias))
+          fail(CEP_E_PARSE, wn + ": " + ref + " in " + q.win_attr + " names neither the stream " + q.stream +
+                                (q.alias.empty() ? std::string() : " nor its alias " + q.alias));
+      }
+      const int col = sd.index(attr);
+      if (col < 0)
+        fail(CEP_E_PARSE, wn + ": " + attr + " is not an attribute of stream " + sd.id);
+      if (sd.attrs[col].type != T_LONG)
+        fail(CEP_E_PARSE, wn + ": the time attribute " + attr + " must be long, it is " +
+                              type_name(sd.attrs[col].type));
+      out.win_col = col;
+    }
+    if (!q.partitioned)
+      fail(CEP_E_UNSUPPORTED, wn + " outside a partition is not supported (one batch window per partition key "
+                                   "only: partition the query)");
+    if (!q.win_events.empty() && q.win_events != "current")
+      fail(CEP_E_UNSUPPORTED, "insert " + q.win_events + " events on a " + wn + " query is not supported "
+                                  "(only current events are emitted)");
+    if (!agg)
+      fail(CEP_E_UNSUPPORTED, wn + " without an aggregate (sum, count, avg, min, max) in the select list is not "
+                                   "supported: its rows would be the input rows, delayed");
+    if (q.group_by.size() > 1 || (q.group_by.size() == 1 && q.group_by[0]->col != out.part_col))
+      fail(CEP_E_UNSUPPORTED, wn + " with group by on anything but the partition key is not supported (it would "
+                                   "emit one row per group per batch)");
+    out.win_kind = q.win_kind;
+    out.win_param = q.win_param;
+  } else if (q.win_kind != WIN_NONE) {
     if (!q.win_events.empty() && q.win_events != "current")
       fail(CEP_E_UNSUPPORTED, "insert " + q.win_events + " events on a window query is not supported "
                                   "(only current events are emitted)");
@@ -1888,6 +1960,10 @@ void compile_join(CompiledApp* app, QueryAst& q) {
   if (sb < 0) fail(CEP_E_UNDEFINED_STREAM, "stream " + q.stream2 + " is not defined");
   if (q.partitioned) fail(CEP_E_UNSUPPORTED, "a join inside `partition with` is not supported");
   if (sa == sb) fail(CEP_E_UNSUPPORTED, "a self-join (join of stream " + q.stream + " with itself) is not supported");
+  for (int kind : {q.win_kind, q.win_kind2})
+    if (win_is_batch(kind))
+      fail(CEP_E_UNSUPPORTED, std::string("#window.") + win_name(kind) + " on a join side is not supported (join "
+                              "sides take #window.length(N) or #window.time(T))");
   if (q.win_kind == WIN_NONE || q.win_kind2 == WIN_NONE)
     fail(CEP_E_UNSUPPORTED, "a join side without a window is not supported: both sides need #window.length(N) "
                             "or #window.time(T)");
@@ -2084,6 +2160,10 @@ bool compile_table_query(CompiledApp* app, QueryAst& q) {
   if (named.empty()) return false;
   const std::string tid = *named.begin();
   const std::string what = "table " + tid + ": ";
+  for (int kind : {q.win_kind, q.win_kind2})
+    if (win_is_batch(kind))
+      fail(CEP_E_UNSUPPORTED, what + "#window." + win_name(kind) + " on a query that names a table (a table writer, "
+                                     "a join against a table, `in`) is not supported");
   if (!q.single)
     fail(CEP_E_UNSUPPORTED, what + (writes && !state_table ? "a pattern or sequence query that writes a table is not supported"
                                                            : "a table in a pattern or sequence is not supported"));

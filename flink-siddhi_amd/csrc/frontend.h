@@ -6,7 +6,8 @@
 //   SiddhiAppRuntime.getStreamDefinitionMap for output-type inference
 //                                         (SiddhiTypeFactory.java:64-112)
 // Unsupported-but-valid SiddhiQL (outer / unidirectional joins, windows other
-// than sliding #window.length / #window.time, tables without a primary key or
+// than sliding #window.length / #window.time and tumbling #window.lengthBatch /
+// #window.externalTimeBatch, tables without a primary key or
 // addressed by anything but that key, extensions) fails with
 // CEP_E_UNSUPPORTED so the Java shim can fall back to real Siddhi.
 #pragma once
@@ -76,6 +77,10 @@ struct Query {
   // the engine keeps one window per key
   int win_kind = WIN_NONE;
   int64_t win_param = 0;         // rows (length) / ms (time)
+  // tumbling windows (#window.lengthBatch(N) / #window.externalTimeBatch(c, T),
+  // batch_kernels.hip): win_kind is WIN_LENGTH_BATCH / WIN_TIME_BATCH; win_col
+  // is c's column, carried as record word win_word (-1: lengthBatch)
+  int win_col = -1, win_word = -1;
   bool win_global = false;       // Siddhi's window spans every group (group by without a
                                  // partition): per-key windows are equivalent only for
                                  // #window.time over non-decreasing ts (engine.cpp)

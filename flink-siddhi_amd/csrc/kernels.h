@@ -316,6 +316,43 @@ struct WinArgs {
   unsigned int* err;
 };
 
+// ---------------------------- tumbling-window aggregates (batch_kernels.hip) --
+// `from S[f]#window.lengthBatch(N) | #window.externalTimeBatch(c, T) select
+// <aggregates> ...` inside a partition: a group-by query
+// (pat.agg_mode = 1) whose per-key state is the open batch.  One row leaves
+// per closed batch: the batch's last row for which `having` held, with the
+// aggregates as of that row (the candidate).  One slot of pat.slot_words
+// words per key in the WalkArgs layout (word w of key idx at kslot[w *
+// kstride + idx]), khdr[idx] = 1 once the key has state:
+//   words [0, nagg)      accumulator of aggregate j over the open batch (count: unused)
+//   word nagg            rows in the open batch (bits 0-31) | a candidate exists << 32
+//   word time_w, + 1     externalTimeBatch: start, end (time_w = -1: lengthBatch)
+//   candidate block (cand_w = -1: lengthBatch without having, whose candidate is the trigger)
+//     cand_acc_w + j     its accumulators, cand_acc_w + nagg its row count (having only, else
+//                        -1: the candidate is the batch's last row and its values the batch's)
+//     cand_w             its event ts
+//     cand_w + 1 + c     its carried record word c (pat.nrec_a of them)
+struct BatchArgs {
+  VmArgs vm;
+  PatternArgs pat;
+  int32_t kind;                  // WIN_LENGTH_BATCH / WIN_TIME_BATCH
+  int64_t param;                 // rows / ms
+  int32_t time_word;             // externalTimeBatch: carried record word of the time attribute
+  int32_t time_w, cand_w, cand_acc_w;
+  const uint64_t* recs;          // k_partition's output, unchanged
+  const uint16_t* tile_off;
+  int32_t ntiles;
+  int32_t tile_rows;
+  const int64_t* chunk_base;
+  uint32_t* khdr;
+  uint64_t* kslot;
+  int64_t kstride;
+  OutArgs out;
+  unsigned int* err;
+};
+// vm: having or computed select items
+void launch_batchwalk(const BatchArgs& a, int nbuckets, bool vm, hipStream_t s);
+
 // ------------------------------------------- event tables (tab_kernels.hip) --
 // `@PrimaryKey('k') define table T (...)` with its writers (insert, update or
 // insert, update, delete) and readers (lookup join, `in`): DESIGN §11.  One

@@ -99,7 +99,14 @@ constexpr int kMaxStates = 6;     // states of an N-state pattern / sequence
 enum AggFn { AGG_SUM = 0, AGG_COUNT = 1, AGG_AVG = 2, AGG_MIN = 3, AGG_MAX = 4 };
 
 // Sliding window of a group-by query (Query::win_kind, WinArgs::kind).
-enum WinKind : int32_t { WIN_NONE = 0, WIN_LENGTH = 1, WIN_TIME = 2 };
+// WIN_LENGTH_BATCH / WIN_TIME_BATCH: the tumbling windows #window.lengthBatch(N)
+// and #window.externalTimeBatch(c, T) (Query::win_col = c; BatchArgs::kind).
+enum WinKind : int32_t { WIN_NONE = 0, WIN_LENGTH = 1, WIN_TIME = 2, WIN_LENGTH_BATCH = 3, WIN_TIME_BATCH = 4 };
+inline constexpr bool win_is_batch(int kind) { return kind == WIN_LENGTH_BATCH || kind == WIN_TIME_BATCH; }
+inline constexpr const char* win_name(int kind) {
+  return kind == WIN_LENGTH ? "length" : kind == WIN_TIME ? "time" : kind == WIN_LENGTH_BATCH ? "lengthBatch"
+       : kind == WIN_TIME_BATCH ? "externalTimeBatch" : "";
+}
 
 // Interpreter-free `on` condition of a windowed stream join: a conjunction of
 // up to kMaxTerms comparisons `a.x op b.y` between plain attributes of one

@@ -220,6 +220,10 @@ struct PatternRT {
   // (kind, param, ring, entry layout); win.kind = WIN_NONE: not a window query
   WinArgs win{};
   bool win_vm = false;         // k_winwalk needs the interpreter (having, computed select items)
+  // tumbling-window aggregate (batch_kernels.hip): the window and state-layout
+  // fields of BatchArgs; bat.kind = WIN_NONE: not a batch-window query.  Its
+  // interpreter flag is win_vm too (a query has one window).
+  BatchArgs bat{};
 };
 
 // Multi-query group (mq_kernels.hip): keyed queries of one app sharing a

@@ -341,6 +341,11 @@ uint64_t plan_hash(const CompiledApp& app) {
     if (q.win_kind == WIN_NONE) continue;
     const int64_t w[4] = {(int64_t)qi, q.win_kind, q.win_param, q.win_global ? 1 : 0};
     mix(w, sizeof(w));
+    // tumbling windows: the time attribute's column (sliding plans hash as before)
+    if (win_is_batch(q.win_kind)) {
+      const int64_t c = q.win_col;
+      mix(&c, sizeof(c));
+    }
   }
   // joins: sides, windows, carried columns (plans without a join hash as before)
   for (size_t qi = 0; qi < app.queries.size(); ++qi) {

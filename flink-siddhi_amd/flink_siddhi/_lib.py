@@ -61,8 +61,10 @@ class UnsupportedPlanException(SiddhiError):
     its partner or read as an `or` side by a later condition), outer joins, tables without a
     primary key or addressed by anything but that key, stream functions, and every window but the sliding `#window.length(N)` /
     `#window.time(T)` aggregates whose window instance is the aggregate group
-    (batch / external-time windows, a length window shared by several groups,
-    a filter after the window, expired-event output; include/cep.h)."""
+    and the tumbling `#window.lengthBatch(N)` / `#window.externalTimeBatch(c, T)`
+    aggregates inside a partition (`#window.timeBatch`, `#window.externalTime`,
+    a batch window outside a partition, a length window shared by several
+    groups, a filter after the window, expired-event output; include/cep.h)."""
     code = CEP_E_UNSUPPORTED
 
 

@@ -58,6 +58,29 @@
  * all events` and windows on pattern states are CEP_E_UNSUPPORTED.
  * A window query without aggregates is the plain projection.
  *
+ * Tumbling windows: inside `partition with (k of S)`, with no group by or
+ * `group by k`, a query with at least one aggregate may instead put
+ * `#window.lengthBatch(N)` (1 <= N <= 2^31 - 1) or
+ * `#window.externalTimeBatch(c, T)` (c a long attribute of S, T >= 1 ms as for
+ * #window.time) after its filter: one window per partition key, one output
+ * row per closed batch.  lengthBatch: the row joins the batch, which closes
+ * when it holds N rows (the row is the trigger).  externalTimeBatch: the key's
+ * first row sets start = c, end = c + T; a later row with c >= end closes the
+ * batch (it is the trigger and not a member) and sets end = c + (T - ((c -
+ * start) mod T)); then the row joins.  The rule is positional (c in any
+ * order, either ts_order); int64 arithmetic, inputs where c + T overflows are
+ * out of contract.  A closing batch folds its rows oldest first into fresh
+ * aggregates (fp64 sums start at +0.0), evaluates having after each row and
+ * emits the last row for which it held, with that row's attributes and the
+ * aggregates as of that row; none: nothing.  Output stamps: ts is the event
+ * ts of the row whose values the output carries, the arrival number (seq) is
+ * the trigger's (ordered_output orders by it).  A batch that never closes
+ * never emits: neither cep_flush nor a watermark closes it.  Outside a
+ * partition, with group by on another attribute, without an aggregate, with
+ * the optional third to fifth arguments of externalTimeBatch, on a join side,
+ * a pattern state or a query that names a table, and #window.timeBatch /
+ * #window.externalTime: CEP_E_UNSUPPORTED.
+ *
  * Join queries: `from A[f]#window.wa [as a] join B[g]#window.wb [as b] on C
  * select ... insert [current events] into O`, an inner join of two different
  * streams with identical definitions, each side behind #window.length(N) (1
@@ -150,7 +173,8 @@ extern "C" {
  *                             forms listed above, outer / unidirectional
  *                             joins and the other join forms listed above,
  *                             windows other than sliding #window.length /
- *                             #window.time):
+ *                             #window.time and tumbling #window.lengthBatch /
+ *                             #window.externalTimeBatch):
  *                             shim falls back to real Siddhi
  *   CEP_E_ARG              -> IllegalArgumentException
  *                             (operator/StreamOutputHandler.java:89)
