@@ -289,6 +289,8 @@ int create_runtime(cep_app* a) {
         p.st_walk[j] = st.walk.off;
         p.st_logic |= st.logic << (2 * j);
         p.stream_mask |= 1 << st.stream;
+        // a pattern with a count state: the walk's third instance
+        if (!q.sequence && (st.min_count != 1 || st.max_count != 1)) p.nfa_mode = kNfaModeCount;
       }
       for (int j = 0; j < p.nstates; ++j) {
         bool opt = true;

@@ -197,6 +197,7 @@ struct State {
   std::string alias, stream;
   ExprP cond;
   int min_count = 1, max_count = 1;
+  char count_op = 0;   // the count was written as a postfix `+`, `*` or `?`
   int logic = 0;   // first side of a logical group: 1 `and` / 2 `or` with the next state
 };
 
@@ -690,9 +691,9 @@ class Parser {
     }
     if (peek().k == TK_OP && peek().v == "#")
       fail(CEP_E_UNSUPPORTED, "a window / stream function on a pattern or sequence state is not supported");
-    if (accept(TK_OP, "+")) { s.min_count = 1; s.max_count = -1; }
-    else if (accept(TK_OP, "*")) { s.min_count = 0; s.max_count = -1; }
-    else if (accept(TK_OP, "?")) { s.min_count = 0; s.max_count = 1; }
+    if (accept(TK_OP, "+")) { s.min_count = 1; s.max_count = -1; s.count_op = '+'; }
+    else if (accept(TK_OP, "*")) { s.min_count = 0; s.max_count = -1; s.count_op = '*'; }
+    else if (accept(TK_OP, "?")) { s.min_count = 0; s.max_count = 1; s.count_op = '?'; }
     else if (peek().k == TK_OP && peek().v == "<" && peek(1).k == TK_NUM) {
       next();
       s.min_count = std::stoi(next().v);
@@ -1628,9 +1629,10 @@ int index_of(std::vector<int>& v, int x, bool add) {
   return (int)v.size() - 1;
 }
 
-// N-state patterns and sequences (with count states in sequences): one NFA
+// N-state patterns and sequences (with count states in either): one NFA
 // lane per key in the walk.  Semantics follow oracle/siddhi_oracle.py
-// (_pattern_event / _sequence_event).
+// (_pattern_event / _sequence_event); a pattern's
+// count states follow DESIGN §14 (compile_pattern has checked them).
 void compile_nfa(CompiledApp* app, QueryAst& q) {
   const int n = (int)q.states.size();
   if (n < 1 || n > kMaxStates) fail(CEP_E_UNSUPPORTED, "patterns / sequences of more than 6 states");
@@ -1639,8 +1641,6 @@ void compile_nfa(CompiledApp* app, QueryAst& q) {
     if (app->input_index(st.stream) < 0)
       fail(CEP_E_UNDEFINED_STREAM, "stream " + st.stream + " is not defined");
     if (j > 0 && st.every) fail(CEP_E_UNSUPPORTED, "'every' on a non-start state");
-    if (!q.sequence && (st.min_count != 1 || st.max_count != 1))
-      fail(CEP_E_UNSUPPORTED, "count states in patterns are not supported");
     for (int k = 0; k < j; ++k)
       if (q.states[k].alias == st.alias && !st.alias.empty()) fail(CEP_E_PARSE, "duplicate state alias");
   }
@@ -1804,11 +1804,38 @@ bool check_logical(const QueryAst& q) {
   return any;
 }
 
+// Count states in a pattern (`x=X[g]<m:n>`): the forms refused by
+// name.  Returns whether the pattern has one; a sequence's counts are the
+// sequence walk's own.
+bool check_counts(const QueryAst& q, bool logical) {
+  if (q.sequence) return false;
+  bool any = false;
+  const int n = (int)q.states.size();
+  for (int j = 0; j < n; ++j) {
+    const State& s = q.states[j];
+    if (s.min_count == 1 && s.max_count == 1 && !s.count_op) continue;
+    any = true;
+    if (s.count_op)
+      fail(CEP_E_UNSUPPORTED, std::string("the postfix '") + s.count_op + "' on a pattern state is sequence syntax "
+                                  "and is not supported: write the count as <m:n>");
+    if (s.max_count == 0 || (s.max_count > 0 && s.min_count > s.max_count))
+      fail(CEP_E_PARSE, "a count <m:n> needs m <= n and n >= 1");
+    if (s.min_count == 0)
+      fail(CEP_E_UNSUPPORTED, "a count state that may be empty (<0:n>) in a pattern is not supported");
+    if (j == 0) fail(CEP_E_UNSUPPORTED, "a count state as the first pattern position is not supported");
+    if (logical)
+      fail(CEP_E_UNSUPPORTED, "a pattern with both a logical group (and / or) and a count state is not supported");
+  }
+  return any;
+}
+
 void compile_pattern(CompiledApp* app, QueryAst& q) {
-  bool counts = false;
-  for (auto& s : q.states) counts |= s.min_count != 1 || s.max_count != 1;
-  if (check_logical(q)) return compile_nfa(app, q);
-  if (q.sequence || q.states.size() != 2 || counts) return compile_nfa(app, q);
+  const bool logical = check_logical(q);
+  // a pattern with a count state, two-position ones included, is walked by
+  // the N-state walk: its partials carry the state word that holds the count
+  const bool counts = check_counts(q, logical);
+  if (logical || counts) return compile_nfa(app, q);
+  if (q.sequence || q.states.size() != 2) return compile_nfa(app, q);
   // s2's condition reads s1: the N-state walk (its pending lists continue in
   // the pending pool, so no key runs out of slots); CEP_PAIR_WALK=1 keeps the
   // two-state walk (lists of pending_slots)
@@ -1818,8 +1845,6 @@ void compile_pattern(CompiledApp* app, QueryAst& q) {
   for (auto& s : q.states) {
     if (app->input_index(s.stream) < 0)
       fail(CEP_E_UNDEFINED_STREAM, "stream " + s.stream + " is not defined");
-    if (s.min_count != 1 || s.max_count != 1)
-      fail(CEP_E_UNSUPPORTED, "count states in patterns are not supported");
   }
   if (q.states[1].every) fail(CEP_E_UNSUPPORTED, "'every' on a non-start state");
   if (q.states[0].alias == q.states[1].alias) fail(CEP_E_PARSE, "duplicate state alias");

@@ -106,6 +106,8 @@ struct FilterArgs {
 };
 
 // ------------------------------------------------------- keyed pattern --
+constexpr int kNfaModeCount = 2;   // PatternArgs::nfa_mode of a pattern with a count state
+
 // `[every] s1=A[f] -> s2=B[g] [within W]` under `partition with`.
 struct PatternArgs {
   int32_t a_stream, b_stream;
@@ -141,7 +143,9 @@ struct PatternArgs {
   int32_t agg_word[kMaxAggs];      // carried word of the argument (-1: count())
   int32_t having_prog;             // -1: none (LDCOL = carried word, LDAGG = running value)
   // N-state pattern / sequence (nfa_mode = 1): one NFA lane per key; a
-  // partial is a state slot {start ts, state | count << 8, captures...}
+  // partial is a state slot {start ts, state | count << 8, captures...};
+  // nfa_mode = kNfaModeCount (2): a pattern with a count state,
+  // whose state word holds the count as a sequence's does
   int32_t nfa_mode;
   int32_t nfa_pair;                // 1: a 2-state pattern's records and state layout (roles
                                    // A / B / G, slots {ts, -, s1 captures}) walked by the

@@ -1392,8 +1392,14 @@ __device__ uint32_t agg_key(const WalkArgs& a, WalkLds& L, uint64_t* R, int k, i
 // are dropped, advanced partials move behind the ones that stayed, a start
 // event appends a new partial.  A logical position (`B and C`, `B or C`:
 // st_logic) is two states sharing one place in the chain; a
-// pattern's state word has no count, so its bits 8-9 say which sides are
+// pattern's state word then has no count, so its bits 8-9 say which sides are
 // filled, and a half-filled `and` partial keeps its place in the list.
+// A pattern with a count state (`B<m:n>`) keeps the count in the
+// state word as a sequence does: a partial at (j, c) awaits state j + 1 once
+// c >= min_j and state j itself while c < max_j, the next state first; it
+// moves behind the partials that stayed at the event that brings a state's
+// count to its min, keeps its place at every other collected event, and a
+// last count state emits once, at min.  Such a plan has no logical position.
 // Sequences: every event of the query's streams
 // either advances a partial (staying in a count state, or moving to a later
 // state skipping optional ones) or discards it.  Matches reserve output rows
@@ -1453,9 +1459,15 @@ __device__ __forceinline__ void nfa_emit(const WalkArgs& a, uint64_t* R, const u
   emit_row<kVm>(a, R, env, key_value(p, kl), rec_seq(rec, seq_base), pos);
 }
 
-// kLogic: the plan has a logical position (PatternArgs::st_logic != 0); plans
-// without one run the instance that has no trace of the transition.
-template <bool kVm, bool kLogic>
+// kMode: kNfaLogic, the plan has a logical position (PatternArgs::st_logic
+// != 0); kNfaCount, a pattern with a count state (PatternArgs::nfa_mode ==
+// kNfaModeCount).  A plan has at most one of the two, and plans with neither
+// run the instance that has no trace of either transition.  k_walk tests for
+// the plain plan first: with the count plan first the kernel spilled six more
+// SGPRs.
+enum NfaMode { kNfaPlain = 0, kNfaLogic = 1, kNfaCount = 2 };
+
+template <bool kVm, int kMode>
 __device__ __noinline__ void nfa_key(const WalkArgs& a, WalkLds& L, uint64_t* R, int k, int bucket, int kpb,
                         int64_t ts_base, int64_t seq_base) {
   const PatternArgs& p = a.pat;
@@ -1534,13 +1546,59 @@ __device__ __noinline__ void nfa_key(const WalkArgs& a, WalkLds& L, uint64_t* R,
       int nf = 0;   // advanced partials, staged in slots [CAP, 2 CAP)
       for (int i = 0; i < n; ++i) {
         uint64_t* si = NSLOT(i);
+        if (kMode == kNfaCount) {
+          // count states: the partial sits at state j with c
+          // events collected there, c < max_j (a state that reaches its max
+          // is stored as (j + 1, 0)).  It awaits state j + 1 once c >= min_j,
+          // and state j itself; the next state is tried first.
+          const uint64_t w = si[st];
+          const int j = (int)(w & 0xffu), c = (int)(w >> 8);
+          const bool nx = j + 1 < N && c >= p.st_min[j] && p.st_stream[j + 1] == stream;
+          const bool cur = p.st_stream[j] == stream;
+          if (!nx && !cur) { copy_slot(m++, i); continue; }
+          if (p.within >= 0) {
+            const int64_t d = ts - (int64_t)si[0];
+            if ((d < 0 ? -d : d) > p.within) continue;   // expired: dropped
+          }
+          int tj, tc;
+          if (nx && nfa_cond<kVm>(a, R, j + 1, role, si, st, rec, ts_base)) {
+            tj = j + 1;
+            tc = 1;
+          } else if (cur && nfa_cond<kVm>(a, R, j, role, si, st, rec, ts_base)) {
+            tj = j;
+            tc = c + 1;
+          } else {
+            copy_slot(m++, i);
+            continue;
+          }
+          const bool at_min = tc == p.st_min[tj];
+          if (at_min && tj == N - 1) {
+            nfa_collect(p, si, st, tj, tc, rec);
+            nfa_emit<kVm>(a, R, si, st, rec, ts_base, seq_base, kl);   // consumed
+            continue;
+          }
+          const uint64_t nw = (p.st_max[tj] >= 0 && tc >= p.st_max[tj])
+                                  ? (uint64_t)(uint32_t)(tj + 1)
+                                  : (uint64_t)(uint32_t)tj | ((uint64_t)(uint32_t)tc << 8);
+          if (!at_min) {   // short of min, or already past it: keeps its place
+            nfa_collect(p, si, st, tj, tc, rec);
+            si[st] = nw;
+            copy_slot(m++, i);
+            continue;
+          }
+          copy_slot(CAP + nf, i);   // min reached: behind the partials that stayed
+          nfa_collect(p, NSLOT(CAP + nf), st, tj, tc, rec);
+          NSLOT(CAP + nf)[st] = nw;
+          ++nf;
+          continue;
+        }
         // a 2-state pattern's partials all wait on state 1 (its at-rest slots
         // do not hold the state word)
         int j = p.nfa_pair ? 1 : (int)(si[st] & 0xffu);
         // logical position: states j, j + 1 are its two sides,
         // bits 8-9 of the state word say which are filled; the event counts
         // for the side of its stream, if that side is still open
-        const int lg = (!kLogic || p.nfa_pair) ? 0 : (p.st_logic >> (2 * j)) & 3;
+        const int lg = (kMode != kNfaLogic || p.nfa_pair) ? 0 : (p.st_logic >> (2 * j)) & 3;
         uint32_t filled = 0;
         int nxt = j + 1;
         if (lg) {
@@ -1884,12 +1942,15 @@ __global__ __launch_bounds__(kWalkThreads) void k_walk(WalkArgs a) {
     if (nfa) {
       // ---- N-state pattern / sequence: one NFA lane per key -----------------
       if constexpr (kVm) {
-        if (!p.st_logic) {
+        if (!p.st_logic && p.nfa_mode != kNfaModeCount) {
           for (int k = tid; k < kpb; k += kWalkThreads)
-            if (L.kstart[k + 1] > L.kstart[k]) nfa_key<kVm, false>(a, L, R, k, bucket, kpb, ts_base, seq_base);
+            if (L.kstart[k + 1] > L.kstart[k]) nfa_key<kVm, kNfaPlain>(a, L, R, k, bucket, kpb, ts_base, seq_base);
+        } else if (p.st_logic) {
+          for (int k = tid; k < kpb; k += kWalkThreads)
+            if (L.kstart[k + 1] > L.kstart[k]) nfa_key<kVm, kNfaLogic>(a, L, R, k, bucket, kpb, ts_base, seq_base);
         } else {
           for (int k = tid; k < kpb; k += kWalkThreads)
-            if (L.kstart[k + 1] > L.kstart[k]) nfa_key<kVm, true>(a, L, R, k, bucket, kpb, ts_base, seq_base);
+            if (L.kstart[k + 1] > L.kstart[k]) nfa_key<kVm, kNfaCount>(a, L, R, k, bucket, kpb, ts_base, seq_base);
         }
       }
     } else if (kVm && p.agg_mode) {

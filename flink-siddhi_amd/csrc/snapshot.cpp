@@ -385,6 +385,20 @@ uint64_t plan_hash(const CompiledApp& app) {
     mix(w, sizeof(w));
     for (auto& st : q.nstates) mix(&st.logic, sizeof(st.logic));
   }
+  // count states in patterns: `B<2:4>` and `B<2:5>` compile to the same code
+  // (a sequence's counts stay out, and every other plan hashes as before)
+  for (size_t qi = 0; qi < app.queries.size(); ++qi) {
+    const Query& q = app.queries[qi];
+    bool any = false;
+    for (auto& st : q.nstates) any = any || st.min_count != 1 || st.max_count != 1;
+    if (!any || q.sequence) continue;
+    const int64_t w[2] = {-7, (int64_t)qi};
+    mix(w, sizeof(w));
+    for (auto& st : q.nstates) {
+      mix(&st.min_count, sizeof(st.min_count));
+      mix(&st.max_count, sizeof(st.max_count));
+    }
+  }
   // query chaining (plans without derived streams hash as before)
   for (auto& d : app.derived) {
     const int64_t w[5] = {-1, d.stream, d.producer, d.source, d.stage};

@@ -40,6 +40,26 @@
  * `or` side, a count suffix or `every` on a side, and absent states (`not X
  * for t`, `... and not X`).
  *
+ * Count states in patterns: an elementary state after the first, the last
+ * included, may carry `<m:n>`, `<m:>` or `<n>` with 1 <= m <= n
+ * (`b=B[g]<2:4>`); it is one of the 6 states, may follow another count state
+ * and may read the stream of its neighbour.  The partial collects g-passing
+ * B events; from the m-th on it also awaits the next state, which is tried
+ * first when both read the event's stream, and the first event of the next
+ * state ends the collection; at n the state stops collecting.  A count state
+ * in last position emits one row, at the m-th event.  `within` is checked when
+ * an event arrives on the stream of a state the partial awaits.  Conditions
+ * and select items read `b[i]`, `b[last]` and plain `b` (= `b[0]`); in b's
+ * own condition they are the events collected before the one under test.  An
+ * index never collected reads as the null word below (0, or dictionary id -1
+ * for STRING) in an output row and in a condition alike: null is not
+ * modelled in the interpreter (upstream Siddhi 4.x semantics, DESIGN.md
+ * section 14).  CEP_E_UNSUPPORTED (the message names the construct): a count
+ * state as the first position, one that may be empty (`<0:n>`), the postfix
+ * `+`, `*`, `?` on a pattern state (sequence syntax: write `<m:n>`), and a
+ * pattern with both a logical group and a count state.  `<:n>`, m > n and
+ * n = 0 are CEP_E_PARSE.
+ *
  * Window queries: a single-stream query may put one sliding window after its
  * filter, `from S[f]#window.length(N) ...` (N rows, 1 <= N <= 255) or
  * `from S[f]#window.time(T) ...` (T in ms or with units, >= 1; the clock is
